@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the CytoSPACE linear-assignment hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned -- the headline solve's rowsol, colsol
+(as float64: exact), u, v (float32) and total (float64, one element) -- as DIR/<name>.npy.  The instance is seeded by n alone, so two
+builds run with the same arguments can be compared output for output (24 n bytes: 1.2 MB at n = 50 000).
 
 N > 1: `python bench.py --gpus N` starts its N ranks ITSELF (one child process per GPU, LOCAL_RANK = device), or runs as one
 rank of an external one-process-per-GPU launcher (`python -m <launcher> --nproc-per-node N ... bench.py --gpus N ...`: RANK /
@@ -634,6 +638,17 @@ def make_cost(n, seed):
     return np.random.default_rng(seed).random((n, n)).astype(np.float32)
 
 
+def dump_outputs(out_dir, res):
+    """--dump-outputs: what a caller of lap_solve receives from the last timed step, one .npy per array (float32 / float64 only:
+    the index arrays as float64, exact for any n)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"rowsol": res["rowsol"].astype(np.float64), "colsol": res["colsol"].astype(np.float64),
+              "u": np.asarray(res["u"], np.float32), "v": np.asarray(res["v"], np.float32),
+              "total": np.array([res["total"]], np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def spawn_ranks(args, argv):
     """`python bench.py --gpus N` without a launcher: start the N ranks here (one child process per GPU, LOCAL_RANK = device;
     rank 0 inherits stdout and prints the line), hand them a rendezvous directory, wait.  A failed or stuck rank ends the job."""
@@ -709,9 +724,13 @@ def main():
     ap.add_argument("--oversubscribe", action="store_true", help="allow more ranks than devices (rank r on device r %% devices; no RCCL "
                                                                  "communicator: a self-test of the harness on a one-GPU box)")
     ap.add_argument("--pmc-tag", default="r06", help="profiles/<tag>_pmc_traffic_n<n>.json supplies roofline.traffic")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result (rowsol, colsol, u, v, total) as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args, sys.argv[1:]))
 
@@ -805,6 +824,8 @@ def main():
     elapsed = time.perf_counter() - t0
     if store is not None:
         elapsed = float(store.allreduce_max(elapsed))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
 
     # ---- parity of the headline itself: the committed goldens (required at the default sizes), and size-independent properties
     # on rows drawn again from the generator (the 10 GB matrix is not kept on the host) ----

@@ -181,7 +181,7 @@ void stream_pool_release(hipStream_t s) {
     auto it = g_stream_device.find(s);
     if (it == g_stream_device.end()) return;                      // (not ours: cannot happen)
     std::vector<hipStream_t> &idle = g_idle_streams[it->second];
-    if (idle.size() < 64) { idle.push_back(s); return; }            // (64 hardware queues at most: _lib.py sets GPU_MAX_HW_QUEUES)
+    if (idle.size() < 64) { idle.push_back(s); return; }            // (64 idle streams per device at most)
     g_stream_device.erase(it);
     (void)hipStreamDestroy(s);
 }

@@ -873,3 +873,29 @@ def test_polish_recovers_the_unique_optimum_on_a_near_tie():
     p = lap_solve(c, np.float32, return_info=True, opts=dict(polish=1))
     assert p["info"].polished == 1 and np.array_equal(p["colsol"], o["colsol"]) and np.array_equal(p["rowsol"], o["rowsol"])
     assert abs(p["total"] - opt) <= 1e-12 * max(1.0, abs(opt))
+
+
+def test_bench_dump_outputs_are_the_last_timed_result(tmp_path):
+    # bench.py --dump-outputs DIR: the timed path's last result as DIR/<name>.npy in float32 / float64 -- the same arrays on a second run
+    # with another step count, and what lap_solve returns for the bench's seeded instance; --steps is the number of timed steps
+    import json
+    import subprocess
+    import sys
+    from tools import instances
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n = 2000
+    runs = []
+    for steps in (1, 3):
+        d = tmp_path / f"steps{steps}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "0",
+                            "--n", str(n), "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-4000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == steps and line["ms_per_step"] > 0
+        runs.append({k: np.load(str(d / f"{k}.npy")) for k in ("rowsol", "colsol", "u", "v", "total")})
+    g = lap_solve(instances.uniform_cost(n), np.float32)
+    for k, a in runs[0].items():
+        assert a.dtype in (np.float32, np.float64), k
+        assert np.array_equal(a, runs[1][k]), k
+        assert np.array_equal(a, np.asarray(g[k], a.dtype).reshape(a.shape)), k
