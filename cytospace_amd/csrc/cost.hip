@@ -331,6 +331,32 @@ __global__ __launch_bounds__(256) void colsq_partial(int G, int C, const float *
     part[(int64_t)blockIdx.y * C + c] = s;
 }
 
+// The Euclidean contraction's shift: mu[g] = the mean of the spots' operand over its S columns (float64 sum, stored as float32)
+__global__ __launch_bounds__(256) void row_mean(int Gpad, int S, const float *__restrict__ a, int64_t lda, float *__restrict__ mu) {
+    __shared__ double sh[256];
+    for (int g = blockIdx.x; g < Gpad; g += gridDim.x) {
+        double s = 0.0;
+        for (int c = threadIdx.x; c < S; c += 256) s += (double)a[(int64_t)g * lda + c];
+        sh[threadIdx.x] = s;
+        __syncthreads();
+        for (int w = 128; w > 0; w >>= 1) {
+            if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) mu[g] = (float)(sh[0] / S);
+        __syncthreads();
+    }
+}
+
+// out[g][c] = in[g][c] - mu[g] (one rounding) for c < n, +0.0 in the padding columns n <= c < ld (both Gpad x ld)
+__global__ __launch_bounds__(256) void shift_rows(int Gpad, int n, int64_t ld, const float *__restrict__ in, const float *__restrict__ mu,
+                                                  float *__restrict__ out) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= ld) return;
+    for (int g = blockIdx.y; g < Gpad; g += gridDim.y)
+        out[(int64_t)g * ld + c] = c < n ? (float)((double)in[(int64_t)g * ld + c] - (double)mu[g]) : 0.0f;
+}
+
 // Per-column ranks, ties averaged, 1-based: pandas.DataFrame.rank() defaults, as used by
 // matrix_correlation_spearman (/root/reference/cytospace/common/common.py:202-215).
 // rank_i = #{x_j < x_i} + (#{x_j == x_i} + 1) / 2, exact in float64 order: one workgroup per column; the column is
@@ -417,7 +443,8 @@ constexpr int BM = 128, BN = 128, BK = 32;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // EPI 0: cost = -dot (Pearson / Spearman on standardised operands);
-// EPI 1: cost = sqrt(|a|^2 + |b|^2 - 2 dot) (Euclidean; squared norms in float64, sum and root in float64)
+// EPI 1: cost = sqrt(|a|^2 + |b|^2 - 2 dot) (Euclidean; squared norms in float64, sum and root in float64; cost_gemm hands it both
+//        operands shifted by the spots' per-gene mean)
 template <int EPI>
 __global__ __launch_bounds__(256, 2) void pearson_gemm(int Gpad, int S, int C, const float *__restrict__ A, int64_t lda,
                                                     const float *__restrict__ B, int64_t ldb,
@@ -801,9 +828,24 @@ static int cost_gemm(int euclid, int Gpad, int S, int C, const float *zst, int64
     Events<2> ev;
     if ((rc = ev.create())) return rc;
     const hipEvent_t e0 = ev[0], e1 = ev[1];
-    DevBuf na, nb, part;
+    DevBuf na, nb, part, mu, sst, ssc;
     if (euclid) {
-        // squared column norms of the float32 operands, in float64
+        // The distance does not change when one per-gene constant is subtracted from both operands.  The spots' per-gene mean
+        // makes the contracted terms small and of both signs: on the plain non-negative log-CPM values the partial sums grow, the
+        // truncating MFMA accumulate errs one way, and |a|^2 + |b|^2 - 2 a.b cancels -- 2.7e-6 relative at 36 601 genes against
+        // the float64 distance, 1.4e-7 with the shift (tests/test_cost_precision_gpu.py).  Shifted copies: the operands are the
+        // caller's.
+        if ((rc = mu.alloc((size_t)Gpad * 4, stream)) || (rc = sst.alloc((size_t)Gpad * ldzst * 4, stream)) ||
+            (rc = ssc.alloc((size_t)Gpad * ldzsc * 4, stream)))
+            return rc;
+        hipLaunchKernelGGL(row_mean, dim3(std::min(Gpad, 65535)), dim3(256), 0, stream, Gpad, S, zst, ldzst, mu.as<float>());
+        hipLaunchKernelGGL(shift_rows, dim3((unsigned)((ldzst + 255) / 256), std::min(Gpad, 65535)), dim3(256), 0, stream, Gpad, S, ldzst, zst,
+                           mu.as<float>(), sst.as<float>());
+        hipLaunchKernelGGL(shift_rows, dim3((unsigned)((ldzsc + 255) / 256), std::min(Gpad, 65535)), dim3(256), 0, stream, Gpad, C, ldzsc, zsc,
+                           mu.as<float>(), ssc.as<float>());
+        zst = sst.as<float>();
+        zsc = ssc.as<float>();
+        // squared column norms of the (shifted) float32 operands, in float64
         const int nblk = Gpad / GB + (Gpad % GB ? 1 : 0);
         const int Cmax = S > C ? S : C;
         if ((rc = na.alloc((size_t)S * 8, stream)) || (rc = nb.alloc((size_t)C * 8, stream)) || (rc = part.alloc((size_t)nblk * Cmax * 8, stream))) return rc;
@@ -834,7 +876,8 @@ int cyto_cost_pearson(int Gpad, int S, int C, const float *zst, int64_t ldzst, c
 
 // The other distance metrics of calculate_cost (linear_assignment_solvers.py:53-59) through the same contraction:
 // Spearman = the Pearson epilogue on rank-transformed operands (cyto_transform(CYTO_TRANSFORM_RANK, ...));
-// Euclidean = sqrt(|a|^2 + |b|^2 - 2 a.b) on the plain float32 operands (cyto_transform(CYTO_TRANSFORM_RAW, ...)).
+// Euclidean = sqrt(|a|^2 + |b|^2 - 2 a.b) on the plain float32 operands (cyto_transform(CYTO_TRANSFORM_RAW, ...)), both shifted by the
+// spots' per-gene mean first (in copies: the operands are not modified).
 int cyto_cost_metric(int metric, int Gpad, int S, int C, const float *zst, int64_t ldzst, const float *zsc, int64_t ldzsc,
                      const int64_t *slots, float *cost_dev, int64_t ldc, double *gemm_ms, int device_id, void *stream_) {
     if (metric < CYTO_METRIC_PEARSON || metric > CYTO_METRIC_EUCLIDEAN) return CYTO_ERR_BAD_ARG;
