@@ -11,7 +11,7 @@
 //       work: a full-chip streaming pass (float4 per lane, >= 2k workgroups).
 //   rows_same_as_prev / rows_group_ids : runs of bitwise identical rows (CytoSPACE repeats every spot row
 //       slots[s] times); used to elide provably useless scans in the augmentation.
-//   build_row_caches<CH> / build_row_caches_stream : per row, the <= 63 columns with the smallest reduced cost
+//   build_row_caches_wave / replicate_group_caches : per row, the <= 63 columns with the smallest reduced cost
 //       plus a floor that bounds every other column (a certificate while prices only decrease).
 //   jv_chain2<CH, LDS_STATE> : REDUCTION TRANSFER + AUGMENTING ROW REDUCTION, a chain of dependent row scans.
 //       One persistent 512-thread workgroup; a scan is served from the row's cache by wave 0 alone whenever the
@@ -1072,7 +1072,7 @@ __global__ __launch_bounds__(BLOCK) void jv_chain_stream(ChainArgs<T> a) {
 // recomputed cached value is < F_i, the cached top-2 IS the exact lexicographic top-2 of the
 // whole row (bit-identical to the full scan).  Otherwise the row is re-scanned from HBM by the
 // whole workgroup (and its cache rebuilt).  The caches of all rows are built once, right after
-// the column reduction, by a full-chip streaming kernel (build_row_caches).
+// the column reduction, by a full-chip streaming kernel (build_row_caches_wave).
 //
 // A cached step runs on ONE wave (lane = cache entry, lane 63 carries the floor): two coalesced
 // 256-B loads, LDS gathers of v and colsol, three 32-bit DPP all-reduces on order-preserving float
@@ -1276,34 +1276,6 @@ __device__ __forceinline__ K2 refresh_row(int i, int n, int64_t ld, const float 
     return g;
 }
 
-// Caches for all rows against the post-column-reduction prices: a full-chip streaming pass.
-template <int CH>
-__global__ __launch_bounds__(BLOCK2) void build_row_caches(int n, int64_t ld, const float *__restrict__ cost,
-                                                          const float *__restrict__ v, uint32_t *__restrict__ cache_col,
-                                                          float *__restrict__ cache_val, const int32_t *__restrict__ rowmap,
-                                                          const int32_t *__restrict__ same_prev) {
-    constexpr int NC = CH * 4;
-    __shared__ Scratch2 s;
-    const int tid = threadIdx.x;
-    int par = 0;
-    float vreg[NC];
-    uint64_t validm = 0;
-#pragma unroll
-    for (int sl = 0; sl < NC; sl++) {
-        const int c = SLOT_COL(sl);
-        vreg[sl] = 0.0f;
-        if (c < n) { validm |= (1ull << sl); vreg[sl] = v[c]; }
-    }
-    float delta = 0.0f;
-    // (a contiguous range of rows per workgroup, not a stride: with runs of identical rows -- ten per spot at c3 -- a stride that
-    //  shares a factor with the run length leaves the first rows of the runs, the only ones that are built, to a few workgroups)
-    const int per = (n + (int)gridDim.x - 1) / (int)gridDim.x, i_end = min(n, ((int)blockIdx.x + 1) * per);
-    for (int i = (int)blockIdx.x * per; i < i_end; i++) {
-        if (same_prev && same_prev[i]) continue;                          // a copy of the previous row: replicate_group_caches
-        (void)refresh_row<CH>(i, n, ld, RBASE(cost, rowmap, i, ld), vreg, validm, cache_col, cache_val, delta, s, par);
-    }
-}
-
 // Runs of bitwise identical consecutive rows (same_prev[i] = row i equals row i - 1: rows_same_as_prev / rows_same_from_map --
 // CytoSPACE repeats every spot row slots[s] times) have identical caches: the build kernels make the cache of the first row of
 // every run, this one copies it to the others (a wave per run; c3: ten rows per spot -- a tenth of the cache-build work).
@@ -1427,25 +1399,11 @@ __device__ __forceinline__ K2 refresh_row_stream(int i, int n, int64_t ld, const
     return g;
 }
 
-__global__ __launch_bounds__(BLOCK2) void build_row_caches_stream(int n, int64_t ld, const float *__restrict__ cost,
-                                                                 const float *v, uint32_t *__restrict__ cache_col,
-                                                                 float *__restrict__ cache_val, const int32_t *__restrict__ rowmap,
-                                                                 const int32_t *__restrict__ same_prev) {
-    __shared__ Scratch2 s;
-    int par = 0;
-    float delta = 0.0f, tau_guess = INFINITY;
-    const int per = (n + (int)gridDim.x - 1) / (int)gridDim.x, i_end = min(n, ((int)blockIdx.x + 1) * per);      // (see build_row_caches)
-    for (int i = (int)blockIdx.x * per; i < i_end; i++) {
-        if (same_prev && same_prev[i]) continue;                          // a copy of the previous row: replicate_group_caches
-        (void)refresh_row_stream<0>(i, n, ld, RBASE(cost, rowmap, i, ld), v, cache_col, cache_val, delta, tau_guess, s, par);
-    }
-}
-
 // ------------------------------------------------------------------------------------------------------------------------------
 // The full-chip cache build as ONE WAVE PER ROW (round 4; what the build before and between the solver's phases runs).  The
-// workgroup forms above hold a row in 187 VGPRs (CH = 10: one workgroup per CU, its loads never overlap its threshold search --
-// 2.1 TB/s at n = 20 000) or sweep it several times between workgroup barriers (the streaming form: 3.0 TB/s at n = 50 000).
-// Here a wave streams its row ONCE with U quads per lane in flight and no barrier anywhere.  Rows of >= 256 U columns: a streaming
+// round-3 builders were a workgroup per row over refresh_row / refresh_row_stream: a row in 187 VGPRs (CH = 10: one workgroup per
+// CU, its loads never overlap its threshold search -- 2.1 TB/s at n = 20 000) or swept several times between workgroup barriers
+// (the streaming form: 3.0 TB/s at n = 50 000); git history has them.  Here a wave streams its row ONCE with U quads per lane in flight and no barrier anywhere.  Rows of >= 256 U columns: a streaming
 // selection without a guess (cb_stream below: the columns under a falling threshold are compacted into a 768-byte staging line of the
 // wave by ballot as they pass).  Shorter rows, and rows the selection gives up on (ties, an adversarial column order): the floor is
 // guessed (the floor of the wave's previous row; ANY floor that admits <= 63 columns makes a valid cache) and the columns under it are
@@ -1643,7 +1601,7 @@ template <int U>
 __global__ __launch_bounds__(64 * CBW) void build_row_caches_wave(int n, int64_t ld, const float *__restrict__ cost,
                                                                  const float *__restrict__ v, uint32_t *__restrict__ cache_col,
                                                                  float *__restrict__ cache_val, const int32_t *__restrict__ rowmap,
-                                                                 const int32_t *__restrict__ same_prev, int stream, int keep_min) {
+                                                                 const int32_t *__restrict__ same_prev, int stream) {
     __shared__ CbStage stage[CBW];
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // (scalar: row bases and descriptors stay in SGPRs)
     CbStage &st = stage[w];
@@ -1654,19 +1612,6 @@ __global__ __launch_bounds__(64 * CBW) void build_row_caches_wave(int n, int64_t
     float tau_guess = INFINITY, delta = 0.0f;
     for (int i = gw * per; i < i_end; i++) {
         if (same_prev && same_prev[i]) continue;                          // a copy of the previous row: replicate_group_caches
-        if (keep_min > 0) {
-            // A REBUILD (keep_min > 0: the caches hold an earlier build): prices only fall, so a floor stays a lower bound of every
-            // uncached column for good and a cache is as good as the number of its columns that still lie below its floor -- two
-            // certify a bid, one a relaxation.  A row that has keep_min of them is left alone: 512 bytes and 63 price gathers
-            // instead of the row.  (A developer's knob, CYTO_CACHE_KEEP, off by default: by the time a rebuild is due hardly a row
-            // has 32 such columns left -- nothing is skipped -- and leaving rows with 2 ... 16 alone brings more full-row bids than
-            // it saves: few-cell-type 20 000^2 17.7 -> 29.0 / 23.8 / 19.8 / 18.9 ms; the 256-chunk batch is flat.  DESIGN "Tried".)
-            const uint32_t kc0 = cache_col[(int64_t)i * KC + lane];
-            const float kv0 = cache_val[(int64_t)i * KC + lane];
-            const float fl0 = __shfl(kv0, KCU);
-            const bool below = lane < KCU && kc0 != COLSENT && (kv0 - v[kc0]) < fl0;
-            if (__popcll(__ballot(below)) >= keep_min) continue;
-        }
         const float *__restrict__ row = cost + row_off(rowmap, i, ld);
         const __amdgpu_buffer_rsrc_t rrow = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(row), 0, (int)(ld * 4), 0x00020000);
         float tau0 = tau_guess;
@@ -1839,24 +1784,6 @@ __device__ __forceinline__ uint32_t wg_min_u32(uint32_t x, Scratch2 &s, int &par
     return readlane32(r, 0);
 }
 
-#ifdef CYTO_AUG_TRACE
-__device__ long long g_aug_trace[2 << 16];   // -DCYTO_AUG_TRACE (tools/trace_aug_scans.py): per search, cumulative scans and elided scans
-#endif
-// -DCYTO_AUG_PROF (tools/prof_aug_step.sh): s_memtime stamps of wave 0 inside a dense augmentation step
-#ifdef CYTO_AUG_PROF
-__device__ long long g_aug_prof[16];
-#define AP_DECL long long ap_[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ap_t_ = 0;
-#define AP_START ap_t_ = (long long)__builtin_amdgcn_s_memtime();
-#define AP_STAMP(k) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const long long now_ = (long long)__builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); ap_[k] += now_ - ap_t_; ap_t_ = now_; }
-#define AP_WAITVM asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#define AP_FLUSH if (threadIdx.x == 0) { for (int k_ = 0; k_ < 14; k_++) g_aug_prof[k_] += ap_[k_]; g_aug_prof[15] += 1; }
-#else
-#define AP_DECL
-#define AP_START
-#define AP_STAMP(k)
-#define AP_WAITVM
-#define AP_FLUSH
-#endif
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float fmin3_raw(float a, float b, float c) {
     float r;
@@ -1946,8 +1873,6 @@ __device__ __forceinline__ int chain_augment(int n, int64_t ld, const float *__r
     int endofpath = -1;
     int nlog = 0;            // scans logged so far in this search (uniform)
     const int lane = tid & 63, wave = tid >> 6;
-    AP_DECL
-    AP_START
     for (;;) {
         // ---- pick: smallest d; among equal d an unassigned column first, then the lowest column.  ONE workgroup
         // exchange per step: every wave reduces its own columns to a candidate (value, then column among the lanes that
@@ -1959,7 +1884,6 @@ __device__ __forceinline__ int chain_augment(int n, int64_t ld, const float *__r
         for (int m = 1; m < CH; m++) lm = fmin_raw(lm, cm[m]);
         const uint32_t wmin = wave_min_u32(f2ord(lm));
         const float dminw = ord2f(wmin);
-        AP_STAMP(8)
         uint32_t lk = 0xFFFFFFFFu;
         const uint64_t holders = __ballot(lm == dminw && dminw < INFINITY);
         bool one_group = false;
@@ -1998,9 +1922,7 @@ __device__ __forceinline__ int chain_augment(int n, int64_t ld, const float *__r
                 }
             }
         }
-        AP_STAMP(9)
         const uint32_t wlk = wave_min_u32(lk);
-        AP_STAMP(10)
         {
             int32_t iw = -1, gw = 0, skipw = 0, sroww = 0;
             float hw = 0.0f, vjpw = 0.0f;
@@ -2027,14 +1949,12 @@ __device__ __forceinline__ int chain_augment(int n, int64_t ld, const float *__r
                     skipw = ((hsv == stamp) && (hw <= hbv)) ? 1 : 0;
                 }
             }
-            AP_STAMP(11)
             if (lane == 0) {
                 lds_rec *const dst = l_rec + par * NW2 + wave;
                 dst->key = ((uint64_t)wmin << 32) | wlk; dst->row = iw; dst->h = hw; dst->vjp = vjpw; dst->g = gw; dst->skip = skipw; dst->srow = sroww;
             }
         }
         lds_barrier();
-        AP_STAMP(12)
         uint64_t k8 = l_rec[par * NW2 + (lane & (NWV - 1))].key;
         uint64_t kmin = k8;
         kmin = umin64(kmin, dpp64<0xB1>(kmin)); kmin = umin64(kmin, dpp64<0x4E>(kmin));
@@ -2045,7 +1965,6 @@ __device__ __forceinline__ int chain_augment(int n, int64_t ld, const float *__r
         const int32_t rw_row = win->row, rw_g = win->g, rw_skip = win->skip, rw_srow = win->srow;
         const float rw_h = win->h, rw_vjp = win->vjp;
         par ^= 1;
-        AP_STAMP(0)
         const float dmin = ord2f((uint32_t)(kmin >> 32));
         const uint32_t g = (uint32_t)kmin;
         if (g == 0xFFFFFFFFu || !(dmin < INFINITY)) return CYTO_ERR_INTERNAL;
@@ -2063,7 +1982,6 @@ __device__ __forceinline__ int chain_augment(int n, int64_t ld, const float *__r
             if (LEAN || gmode == 1) { l_hb[grp] = h; l_hs[grp] = stamp; }
             else { st_f32(hb + grp, h); st_i32(hs + grp, stamp); }
         }
-        AP_STAMP(1)
         float4 x[CH];
         if (!skip) {
             const int srow = __builtin_amdgcn_readfirstlane(rw_srow);
@@ -2075,7 +1993,6 @@ __device__ __forceinline__ int chain_augment(int n, int64_t ld, const float *__r
             }
             nlog++;
         }
-        AP_STAMP(2)
         {   // retire column jp: remember v+d (price update) and d (predecessor search), mask the column out.
             // The slot is wave-uniform: a scalar branch per slot instead of two selects per slot.
             const int q = jp >> 2;
@@ -2095,17 +2012,13 @@ __device__ __forceinline__ int chain_augment(int n, int64_t ld, const float *__r
                 }
             }
         }
-        AP_STAMP(3)
         if (skip) {
 #pragma unroll
             for (int m = 0; m < CH; m++) cm[m] = fmin_raw(fmin3_raw(DR(m * 4), DR(m * 4 + 1), DR(m * 4 + 2)), DR(m * 4 + 3));
             c_relax++;
             c_skipped++;
-            AP_STAMP(6)
             continue;
         }
-        AP_WAITVM
-        AP_STAMP(4)
         const f32x2 hh = {h, h};
 #pragma unroll
         for (int m = 0; m < CH; m++) {
@@ -2120,11 +2033,9 @@ __device__ __forceinline__ int chain_augment(int n, int64_t ld, const float *__r
             SCHED_FENCE();
         }
         c_relax++;
-        AP_STAMP(5)
     }
     // ---- the augmenting path, from the end column back to the free row (prices are still the search's prices) ----
     __syncthreads();   // the scan log and the retired columns' records are complete
-    AP_START
     {
         int ep = endofpath;
         float dep = curmin;                                   // the end column's distance is the final minimum
@@ -2174,8 +2085,6 @@ __device__ __forceinline__ int chain_augment(int n, int64_t ld, const float *__r
     for (int sl = 0; sl < NC; sl++)
         if ((readym >> sl) & 1) st_vset<LDS_STATE>(s_v, gv, SLOT_COL(sl), ld_f32(&sd[SLOT_COL(sl)].x) - curmin);
     __syncthreads();
-    AP_STAMP(7)
-    AP_FLUSH
 #undef VM
 #undef DR
 #undef SLOT_COL
@@ -2184,26 +2093,6 @@ __device__ __forceinline__ int chain_augment(int n, int64_t ld, const float *__r
 }
 
 enum { PH_RT = 0, PH_ARR = 1, PH_AUG = 2 };
-
-// -DCYTO_ARR_PROF (tools/prof_arr_step.py): s_memtime stamps inside a cached ARR step (the loop runs on wave 0 alone)
-#ifdef CYTO_ARR_PROF
-__device__ long long g_arr_prof[16];
-#define RP_DECL long long rp_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, rp_t_ = 0, rp_n_ = 0;
-#define RP_START rp_t_ = (long long)__builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#define RP_STAMP(k) { const long long now_ = (long long)__builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); rp_[k] += now_ - rp_t_; rp_t_ = now_; }
-#define RP_WAITVM asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#define RP_WAITLDS asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#define RP_COUNT rp_n_++;
-#define RP_FLUSH if (threadIdx.x == 0) { for (int k_ = 0; k_ < 8; k_++) g_arr_prof[k_] = rp_[k_]; g_arr_prof[8] = rp_n_; }
-#else
-#define RP_DECL
-#define RP_START
-#define RP_STAMP(k)
-#define RP_WAITVM
-#define RP_WAITLDS
-#define RP_COUNT
-#define RP_FLUSH
-#endif
 
 // CS_LDS (only meaningful with !LDS_STATE, n <= 65535): the prices are too many for LDS but colsol (u16) still fits;
 // the chain then never stores colsol to global memory (on gfx9 a load is not returned before the stores issued
@@ -2271,7 +2160,6 @@ __global__ __launch_bounds__(BLOCK2) void jv_chain2(const Chain2Args *__restrict
     bool have_dense = false;
     K2 gd; gd.m1 = KEYMAX; gd.m2 = KEYMAX;
     int napp = 0;                           // entries staged in s_app since the last flush
-    RP_DECL
 
     for (;;) {
         if (wave == 0) {
@@ -2349,7 +2237,6 @@ __global__ __launch_bounds__(BLOCK2) void jv_chain2(const Chain2Args *__restrict
                 int pf_row = -1;
                 uint32_t pf_col = 0;
                 float pf_cv = 0.0f;
-                RP_START
                 for (;;) {
                     const int i = cur_i;
                     float umin, usub, vj1, cj1 = 0.0f, cj2 = 0.0f;
@@ -2370,15 +2257,11 @@ __global__ __launch_bounds__(BLOCK2) void jv_chain2(const Chain2Args *__restrict
                             col = ld_u32(a.cache_col + (int64_t)i * KC + lane);
                             cv = ld_f32(a.cache_val + (int64_t)i * KC + lane);
                         }
-                        RP_WAITVM
-                        RP_STAMP(0)                                              // wait for the row's cache (L2)
                         const bool valid = col != COLSENT;
                         const float vj = st_vget<LDS_STATE>(s_v, gv, valid ? (int)col : 0);
                         const int32_t csj = st_csget<CSL>(s_cs, gcolsol, valid ? (int)col : 0);
                         const float F = __uint_as_float(readlane32(__float_as_uint(cv), KCU));
                         const uint32_t ord = valid ? f2ord(cv - vj) : 0xFFFFFFFFu;
-                        RP_WAITLDS
-                        RP_STAMP(1)                                              // LDS gathers of v and colsol
                         // minimum, its lane (ties: lowest column), then the minimum of the rest
                         const uint32_t o1 = wave_min_u32(ord);
                         const uint64_t m1 = __ballot(ord == o1);
@@ -2389,7 +2272,6 @@ __global__ __launch_bounds__(BLOCK2) void jv_chain2(const Chain2Args *__restrict
                             pf_col = ld_u32(a.cache_col + (int64_t)pf_row * KC + lane);
                             pf_cv = ld_f32(a.cache_val + (int64_t)pf_row * KC + lane);
                         }
-                        RP_STAMP(2)                                              // first reduction, lane of the minimum, prefetch issue
                         const uint32_t o2 = wave_min_u32(lane == l1 ? 0xFFFFFFFFu : ord);
                         usub = ord2f(o2);
                         if (__builtin_expect(!(usub < F), 0)) {
@@ -2412,8 +2294,6 @@ __global__ __launch_bounds__(BLOCK2) void jv_chain2(const Chain2Args *__restrict
                         }
                     }
                     c_arr++;
-                    RP_STAMP(3)                                                  // second reduction, read-lanes
-                    RP_COUNT
                     const float vnew = vj1 - (usub - umin);
                     const bool lowers = vnew < vj1;
                     const bool swap = !lowers && i0 >= 0;
@@ -2425,8 +2305,6 @@ __global__ __launch_bounds__(BLOCK2) void jv_chain2(const Chain2Args *__restrict
                         if (lowers) st_vset<LDS_STATE>(s_v, gv, j1, vnew);
                         st_csset<CSL>(s_cs, gcolsol, jj, i);
                     }
-                    RP_WAITLDS
-                    RP_STAMP(4)                                                  // price / colsol update
                     if (__builtin_expect(i0f >= 0 && lowers && c_arr < arr_budget, 1)) { cur_i = i0f; continue; }   // chain goes on
                     if (i0f >= 0) {
                         if (lowers) carry = i0f;       // budget reached: the slow path flushes it
@@ -2478,7 +2356,6 @@ __global__ __launch_bounds__(BLOCK2) void jv_chain2(const Chain2Args *__restrict
         counters[C2_DENSE_REFRESH] = c_dense;
         *reinterpret_cast<int *>(a.misc + 128) = numfree;
     }
-    RP_FLUSH
 }
 
 // AUGMENTATION + duals + total: one persistent workgroup, all lanes active (see chain_augment).
@@ -2564,9 +2441,6 @@ __global__ __launch_bounds__(BS) void jv_aug2(const Chain2Args *__restrict__ bat
             err = chain_augment<CH, LDS_STATE, BS, false>(n, ld, cost, gv, sd, cassign, rowsol, gcolsol, slog_row, slog_h, s_v, s_cs, freerow, validm,
                                                           s, par, c_relax, c_hops, c_skipped, gmode, a.rowgid, a.iws + 6 * (int64_t)n, hb, hs, f + 1,
                                                           s_ca, s_cg, s_rec, a.rowmap);
-#ifdef CYTO_AUG_TRACE
-        if (threadIdx.x == 0 && f < (1 << 16)) { g_aug_trace[2 * f] = c_relax; g_aug_trace[2 * f + 1] = c_skipped; }
-#endif
         c_augs++;
     }
     // ---- write back prices and colsol, then duals u and the total ----
@@ -2662,19 +2536,6 @@ __device__ __forceinline__ void gl_min_u64(uint64_t *p, uint64_t x) {
     (void)__hip_atomic_fetch_min(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// -DLZ_PROF (tools/prof_lazy_step.py): s_memtime stamps of wave 0 inside a cache-certified augmentation step
-#ifdef LZ_PROF
-__device__ long long g_lz_prof[24];
-#define LZ_STAMP(k) { const long long now_ = (long long)__builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt lgkmcnt(0)"); \
-                      if ((k) > 0) prof[k] += now_ - tlast; else if (tlast) prof[0] += 0; tlast = now_; profn[k]++; }
-#define LZ_WAITVM asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#define LZ_STAMP2(k) { const long long now_ = (long long)__builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt lgkmcnt(0)"); \
-                       prof2[k] += now_ - tlast2; tlast2 = now_; }
-#else
-#define LZ_STAMP(k)
-#define LZ_STAMP2(k)
-#define LZ_WAITVM
-#endif
 constexpr uint64_t LZ_INFKEY = 0xFFFFFFFF00000000ull;   // "no distance yet": any real d wins the unsigned min
 // Before a column's word is used in this search its block of 64 words must hold this search's values:
 // blocks are reset lazily (all 64 words = "no distance") the first time a search touches them.
@@ -2703,10 +2564,6 @@ template <bool LDS_STATE, bool CS_LDS = false>
 __global__ __launch_bounds__(BLOCK2) void jv_aug_lazy(const LazyArgs *__restrict__ batch) {
     const LazyArgs a = load_args(batch);         // one workgroup per problem of the batch
     constexpr bool CSL = LDS_STATE || CS_LDS;
-#ifdef LZ_PROF
-    long long prof[6] = {0, 0, 0, 0, 0, 0}, profn[6] = {0, 0, 0, 0, 0, 0}, tlast = 0;
-    long long prof2[4] = {0, 0, 0, 0}, tlast2 = 0;
-#endif
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];
     __shared__ Scratch2 s;
     __shared__ LazyCmd cmd;
@@ -2805,7 +2662,6 @@ __global__ __launch_bounds__(BLOCK2) void jv_aug_lazy(const LazyArgs *__restrict
             while (!post) {
                 if (!insearch) {
                     if (f >= numfree || err || bail) { if (lane == 0) cmd.op = err ? LZ_ERR : LZ_EXIT; break; }
-                    LZ_STAMP2(0)
                     // (freerow, ncc, ncv) were requested during the previous search; request the next ones now
                     const uint32_t cc = ncc;
                     const float cv = ncv;
@@ -2848,7 +2704,6 @@ __global__ __launch_bounds__(BLOCK2) void jv_aug_lazy(const LazyArgs *__restrict
                         f++;
                         freerow = id1_saved;
                         insearch = false;
-                        LZ_STAMP2(1)
                         continue;
                     }
                     if (cert0) {
@@ -2862,7 +2717,6 @@ __global__ __launch_bounds__(BLOCK2) void jv_aug_lazy(const LazyArgs *__restrict
                         if (lane == 0) { s_T = t0; st_i32(a.srow, freerow); }
                         c_sparse++;
                         isparse = true; icc = cc; icv = cv;
-                        LZ_STAMP2(1)
                     } else {
                         if (lane == 0) { cmd.op = LZ_INIT_DENSE; cmd.row = freerow; cmd.stamp = stamp; }
                         isparse = false; dense_used = true; post = true;
@@ -2870,7 +2724,6 @@ __global__ __launch_bounds__(BLOCK2) void jv_aug_lazy(const LazyArgs *__restrict
                     }
                 }
                 for (;;) {
-                    LZ_STAMP(0)
                     // ---- pick: smallest (d, assigned?, column) over the block minima ----
                     uint64_t k = KEYMAX;
                     for (int b0 = 0; b0 < nbp; b0 += 512) {
@@ -2892,11 +2745,9 @@ __global__ __launch_bounds__(BLOCK2) void jv_aug_lazy(const LazyArgs *__restrict
                     const float dmin = key_val(k);
                     if (k == KEYMAX || !(dmin < INFINITY)) { err = CYTO_ERR_INTERNAL; insearch = false; break; }
                     const int jp = (int)((uint32_t)k & 0x7FFFFFFFu);
-                    LZ_STAMP(1)
                     if (!have || dmin != curmin) { level++; curmin = dmin; have = true; }
                     if (!((uint32_t)k & 0x80000000u)) {
                         // ======== end of the search (wave 0 alone): price update, path flip, clean-up ========
-                        LZ_STAMP2(2)
                         const int endofpath = jp;
                         {
                             const int rem = nscan & 63, base = nscan - rem;
@@ -2953,7 +2804,6 @@ __global__ __launch_bounds__(BLOCK2) void jv_aug_lazy(const LazyArgs *__restrict
                         } else {
                             for (int b = lane; b < nb; b += 64) { bmin[b] = KEYMAX; s_sc[2 * b] = 0; s_sc[2 * b + 1] = 0; }
                         }
-                        LZ_STAMP2(3)
                         c_augs++;
                         f++;
                         freerow = id1_saved;
@@ -2985,8 +2835,6 @@ __global__ __launch_bounds__(BLOCK2) void jv_aug_lazy(const LazyArgs *__restrict
                         atomicOr(&s_sc[jp >> 5], 1u << (jp & 31));
                     }
                     const uint32_t scw = s_sc[blk * 2 + (lane >> 5)], unw = s_un[blk * 2 + (lane >> 5)];
-                    LZ_WAITVM
-                    LZ_STAMP(2)
                     const float cip = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(cip_raw)));
                     const float h = (cip - vjp) - curmin;
                     // (the word of a scanned column is never written again -- every writer tests the scanned bit -- so it
@@ -3022,7 +2870,6 @@ __global__ __launch_bounds__(BLOCK2) void jv_aug_lazy(const LazyArgs *__restrict
                         st_i32(a.slist + base + lane, s_ljp[lane]); st_i32(a.slevel + base + lane, s_llv[lane]);
                         st_f32(a.sumvd + base + lane, s_lsv[lane]); st_i32(a.srow + 1 + base + lane, s_lrw[lane]);
                     }
-                    LZ_STAMP(3)
                     if (skip) { c_skipped++; continue; }
                     const float floor_i = __uint_as_float(readlane32(__float_as_uint(cv), KCU));
                     const float T = ord2f(s_T);
@@ -3050,11 +2897,7 @@ __global__ __launch_bounds__(BLOCK2) void jv_aug_lazy(const LazyArgs *__restrict
                             lds_min_u64(bmin + (j >> 6), ((uint64_t)o2 << 32) | (un ? 0u : 0x80000000u) | (uint32_t)j);
                             if (un) atomicMin(&s_T, o2);
                         }
-#ifdef LZ_PROF
-                        prof2[1] += __builtin_popcountll(__ballot(act));
-#endif
                     }
-                    LZ_STAMP(4)
                     if (nexc > 0) {
                         const bool ev = lane < nexc;
                         const int j = ev ? s_exc[lane] : 0;
@@ -3070,7 +2913,6 @@ __global__ __launch_bounds__(BLOCK2) void jv_aug_lazy(const LazyArgs *__restrict
                             if (un) atomicMin(&s_T, o2);
                         }
                     }
-                    LZ_STAMP(5)
                 }
             }
         }
@@ -3255,11 +3097,6 @@ __global__ __launch_bounds__(BLOCK2) void jv_aug_lazy(const LazyArgs *__restrict
         counters[C2_AUG_SPARSE_INIT] = c_sparse;
         *reinterpret_cast<int *>(a.misc + 136) = f;          // searches completed (== numfree unless the kernel gave up)
         *reinterpret_cast<int *>(a.misc + 4) = err;
-#ifdef LZ_PROF
-        for (int k = 0; k < 6; k++) { g_lz_prof[k] = prof[k]; g_lz_prof[6 + k] = profn[k]; }
-        for (int k = 0; k < 4; k++) g_lz_prof[12 + k] = prof2[k];
-        g_lz_prof[16] = c_augs; g_lz_prof[17] = c_relax; g_lz_prof[18] = c_dense; g_lz_prof[19] = c_sparse;
-#endif
     }
 }
 
@@ -3331,8 +3168,6 @@ __global__ __launch_bounds__(1024) void dual_gap_finish(int n, const double *__r
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-static std::atomic<int> g_par_busy[64];     // per device: a several-searches-at-once kernel (wide_aug<..,PAR>) is in flight
-
 static const cyto_lap_opts k_default_opts = {};
 
 static int check_opts(const cyto_lap_opts &o) {
@@ -3341,7 +3176,7 @@ static int check_opts(const cyto_lap_opts &o) {
         return CYTO_ERR_BAD_ARG;
     if (o.group_state_global < 0 || o.group_state_global > 1 || o.aux_state_global < 0 || o.aux_state_global > 1) return CYTO_ERR_BAD_ARG;
     if (o.mode < 0 || o.mode > 2 || o.wide_rounds < -1 || o.wide_groups < -1 || o.wide_groups > 32 || o.wide_rebuild < -1 ||
-        o.wide_wipe < 0 || o.wide_wipe > 2048 || o.wide_par < -1 || o.wide_par > WIDE_PAR_GMAX) return CYTO_ERR_BAD_ARG;
+        o.wide_wipe < 0 || o.wide_wipe > 2048 || o.wide_par < -1 || o.wide_par > WIDE_PAR_GMAX) return CYTO_ERR_BAD_ARG;    // (wide_groups: ignored)
     if (o.cache_waves < -1 || o.cache_waves > 32 || (o.cache_unroll != 0 && o.cache_unroll != 4 && o.cache_unroll != 8) || o.cache_stream < -1 ||
         o.cache_stream > 1)
         return CYTO_ERR_BAD_ARG;
@@ -3369,18 +3204,34 @@ struct F32Job {
     Chain2Args c2; LazyArgs la;
     size_t shm_lazy = 0, shm_aug = 0;
     bool alive() const { return status == CYTO_OK; }
+    const int32_t *rowmap() const { return rowmap_host ? b_rowmap.as<int32_t>() : nullptr; }
+    const int32_t *same(int n) const { return (h_ngroups < n && n >= 2) ? b_same.as<int32_t>() : nullptr; }    // (runs of identical rows)
 };
 
 struct F32Plan {            // what depends on n (and the options) only: identical for every problem of the batch
-    int n, colblocks, rowblocks, rows_per_block, cache_grid;
-    int cache_stream = 1;           // build_row_caches_wave: the guess-free single sweep (cb_stream); 0: a neighbour's floor as the guess
-    int cache_waves = 8, cache_unroll = 4, cus = 256;      // build_row_caches_wave: waves per CU, quads in flight per lane; CUs of the device (device_cus)
-    int cache_keep = 0;             // a REBUILD leaves a row alone that still has this many cached columns below its floor (0: every row)
+    int n, colblocks, rowblocks, rows_per_block;
+    CachePlan cache;
     bool force_l2, lds_variant, lazy, lz_lds_state, lz_cs_lds, no_cs_lds, wide;
-    long long wide_rounds;
-    int wide_groups, wide_rebuild, wide_wipe, wide_par;
     size_t shm_chain, lz_base_shm;
 };
+
+int build_caches(const CachePlan &cp, int n, int64_t ld, const float *cost, const int32_t *rowmap, const float *v, uint32_t *cache_col,
+                 float *cache_val, const int32_t *same, hipStream_t stream) {
+    // (a wave per row; the grid: cp.waves waves on every CU, four to a workgroup)
+    const int g = std::max(1, std::min((n + CBW - 1) / CBW, cp.waves * cp.cus / CBW));
+    if (cp.unroll == 8)
+        hipLaunchKernelGGL(build_row_caches_wave<8>, dim3(g), dim3(64 * CBW), 0, stream, n, ld, cost, v, cache_col, cache_val, rowmap, same,
+                           cp.stream);
+    else
+        hipLaunchKernelGGL(build_row_caches_wave<4>, dim3(g), dim3(64 * CBW), 0, stream, n, ld, cost, v, cache_col, cache_val, rowmap, same,
+                           cp.stream);
+    // (runs of identical rows: one cache per run, copied to the rest)
+    if (same)
+        hipLaunchKernelGGL(replicate_group_caches, dim3(std::max(1, std::min((n + 3) / 4, 2048))), dim3(256), 0, stream, n, same, cache_col,
+                           cache_val);
+    CYTO_HIP(hipGetLastError());
+    return CYTO_OK;
+}
 
 template <int CH, bool LDS_STATE>
 static int launch_batch(const F32Plan &pl, std::vector<F32Job> &jobs, hipStream_t stream, hipEvent_t ev_cache_done,
@@ -3394,36 +3245,12 @@ static int launch_batch(const F32Plan &pl, std::vector<F32Job> &jobs, hipStream_
     const bool cs_lds = !LDS_STATE && n <= 65535 && !pl.no_cs_lds;
     void (*kern)(const Chain2Args *) = jv_chain2<CH, LDS_STATE, false>;
     if constexpr (!LDS_STATE) { if (cs_lds) kern = jv_chain2<CH, false, true>; }
-    bool caches_built = false;                                   // (the first build finds uninitialised memory: nothing to keep)
-    auto build_caches = [&](const int *remaining) -> int {      // remaining: per live problem, 0 = nothing left to do for it (or null)
-        const int keep = (caches_built && pl.wide) ? pl.cache_keep : 0;
-        caches_built = true;
-        for (int k = 0; k < nl; k++) {
-            if (remaining && remaining[k] == 0) continue;
-            const int b = live[k];
+    auto build_all_caches = [&]() -> int {
+        for (int b : live) {
             const Chain2Args &a = jobs[b].c2;
-            // (runs of identical rows: one cache per run, copied to the rest)
-            const int32_t *same = (jobs[b].h_ngroups < n && n >= 2) ? jobs[b].b_same.as<int32_t>() : nullptr;
-            if (pl.cache_waves > 0) {
-                // (a wave per row; the grid: pl.cache_waves waves on every CU, four to a workgroup)
-                const int g = std::max(1, std::min((n + CBW - 1) / CBW, pl.cache_waves * pl.cus / CBW));
-                if (pl.cache_unroll == 8)
-                    hipLaunchKernelGGL(build_row_caches_wave<8>, dim3(g), dim3(64 * CBW), 0, stream, n, a.ld, a.cost, (const float *)a.fws,
-                                       a.cache_col, a.cache_val, a.rowmap, same, pl.cache_stream, keep);
-                else
-                    hipLaunchKernelGGL(build_row_caches_wave<4>, dim3(g), dim3(64 * CBW), 0, stream, n, a.ld, a.cost, (const float *)a.fws,
-                                       a.cache_col, a.cache_val, a.rowmap, same, pl.cache_stream, keep);
-            } else if constexpr (CH == 0)
-                hipLaunchKernelGGL(build_row_caches_stream, dim3(pl.cache_grid), dim3(BLOCK2), 0, stream, n, a.ld, a.cost,
-                                   (const float *)a.fws, a.cache_col, a.cache_val, a.rowmap, same);
-            else
-                hipLaunchKernelGGL((build_row_caches<CH>), dim3(pl.cache_grid), dim3(BLOCK2), 0, stream, n, a.ld, a.cost,
-                                   (const float *)a.fws, a.cache_col, a.cache_val, a.rowmap, same);
-            if (same)
-                hipLaunchKernelGGL(replicate_group_caches, dim3(std::max(1, std::min((n + 3) / 4, 2048))), dim3(256), 0, stream, n, same,
-                                   a.cache_col, a.cache_val);
+            const int r2 = build_caches(pl.cache, n, a.ld, a.cost, a.rowmap, a.fws, a.cache_col, a.cache_val, jobs[b].same(n), stream);
+            if (r2) return r2;
         }
-        CYTO_HIP(hipGetLastError());
         return CYTO_OK;
     };
     // argument blocks of the batch, in `live` order
@@ -3440,150 +3267,8 @@ static int launch_batch(const F32Plan &pl, std::vector<F32Job> &jobs, hipStream_
     CYTO_HIP(hipMemcpyAsync(d_c2.p, h_c2.data(), sizeof(Chain2Args) * nl, hipMemcpyHostToDevice, stream));
     CYTO_HIP(hipMemcpyAsync(d_la.p, h_la.data(), sizeof(LazyArgs) * nl, hipMemcpyHostToDevice, stream));
 
-    if ((rc = build_caches(nullptr))) return rc;
+    if ((rc = build_all_caches())) return rc;
     CYTO_HIP(hipEventRecord(ev_cache_done, stream));
-    struct ParSlot { std::atomic<int> *p = nullptr; ~ParSlot() { if (p) p->store(0); } } par_slot;       // (released on every return path)
-    bool par_slot_held = false;
-    int dev_now = 0;
-    (void)hipGetDevice(&dev_now);
-    const int device_slot = dev_now >= 0 && dev_now < 64 ? dev_now : 0;
-    if (pl.wide) {
-        // the wide solver (lap_wide.hip): Jacobi reduction transfer, Jacobi rounds of row reduction, speculative shortest-path
-        // augmentation -- one launch per phase for the whole batch
-        const size_t nT = (size_t)n * sizeof(float);
-        std::vector<WideArgs> h_wa((size_t)nl);
-        for (int k = 0; k < nl; k++) {
-            F32Job &j = jobs[live[k]];
-            // Both several-workgroup search kernels (wide_aug_mc: one search on G workgroups; wide_aug<.., PAR>: G searches at once) meet at
-            // hand-rolled grid barriers and are launched as plain kernels: their participating workgroups (blocks 0, 8, 16, ... -- one XCD)
-            // must all be RESIDENT, one 1024-thread workgroup per CU.  So G is clamped to the CUs of one XCD, and ONE such kernel runs per
-            // device at a time, whichever of the two it is: workgroups of two of them could each get partly scheduled and spin for the
-            // rest.  A solve that finds the slot taken runs one search at a time on one workgroup (same results).
-            const int xcd_cus = std::max(1, pl.cus / 8);
-            int mcg = nl != 1 ? 0 : (pl.wide_groups > 0 ? pl.wide_groups : (pl.wide_groups < 0 ? 0 : wide_mc_groups(nl, n)));
-            mcg = std::min(mcg, xcd_cus);
-            // several searches of ONE problem at once (wide_aug<.., PAR>): by default for a single problem without runs of identical
-            // rows (those finish their searches as runs of one-edge steps in the one-workgroup kernel) from 2 048 rows on
-            // (runs of identical rows -- a Visium problem's slots: a tenth as many groups as rows -- finish most of their searches as
-            //  runs of one-edge steps in the one-workgroup kernel; a sub-spot chunk's few doubled spots do not matter)
-            const bool dup_rows = n >= 2 && (long long)j.h_ngroups * 5 < (long long)n * 4;
-            int parg = (nl != 1 || mcg > 0) ? 0 : (pl.wide_par > 0 ? pl.wide_par : (pl.wide_par < 0 || dup_rows || n < 2048 ? 0 : 16));
-            parg = std::min(std::min(parg, WIDE_PAR_GMAX), xcd_cus);
-            if (parg == 1) parg = 0;
-            if (mcg == 1) mcg = 0;
-            if (parg > 1 || mcg > 1) {
-                if (g_par_busy[device_slot].exchange(1) != 0) { parg = 0; mcg = 0; }
-                else par_slot_held = true;
-            }
-            if (par_slot_held) par_slot.p = &g_par_busy[device_slot];
-            const size_t mcb = mcg > 0 ? wide_mc_state_bytes(n) : 0;
-            const size_t parb = parg > 0 ? wide_par_state_bytes(n, parg) : 0;
-            const size_t sc_off = ((2 * nT + 255) / 256) * 256 + mcb;       // the phase machine's control block behind everything else
-            const size_t par_off = sc_off + WIDE_SC_BYTES;
-            const size_t scx_off = ((par_off + parb + 255) / 256) * 256;     // the machine's own arrays (lap_wide.hip: ScMem)
-            if ((rc = j.b_wide.alloc(scx_off + wide_sc_ext_bytes(n), stream))) return rc;
-            const Chain2Args &c = j.c2;
-            WideArgs &wa = h_wa[k];
-            wa.n = n; wa.ld = c.ld; wa.cost = c.cost; wa.rowmap = c.rowmap;
-            wa.v = c.fws; wa.u = c.fws + n; wa.cassign = c.fws + 3 * (int64_t)n;
-            wa.label = reinterpret_cast<unsigned long long *>(c.fws + 4 * (int64_t)n);
-            wa.rowsol = c.iws; wa.colsol = c.iws + n; wa.matches = c.iws + 2 * (int64_t)n; wa.freerows = c.iws + 3 * (int64_t)n;
-            wa.act0 = c.iws + 4 * (int64_t)n; wa.act1 = c.iws + 5 * (int64_t)n; wa.touched = c.iws + 6 * (int64_t)n;
-            wa.slot_j = c.iws + 7 * (int64_t)n;
-            wa.bid = reinterpret_cast<unsigned long long *>(c.iws + 8 * (int64_t)n);
-            wa.slot_p = j.b_wide.as<float>(); wa.slot_c = wa.slot_p + n;
-            wa.cache_col = c.cache_col; wa.cache_val = c.cache_val; wa.misc = c.misc;
-            wa.max_rounds = pl.wide_rounds;
-            // (the several-searches kernel never pauses -- it never looks at aug_seg --, but the row reduction's rebuild rule reads the same field)
-            wa.aug_seg = mcg > 0 ? -1 : pl.wide_rebuild;
-            // what a rebuild costs, in full-row relaxations of ONE workgroup (a relaxation sweeps n elements at ~5 G/s; a pass costs
-            // ~0.4 ms of launches and synchronisation plus one read of every unfinished problem's matrix by the whole chip, ~100x
-            // faster per element -- and the problems of a batch are rebuilt one after the other while their workgroups all wait)
-            wa.aug_waste = (int)std::min<long long>(1 << 30, std::max<long long>(16, (2000000ll + (long long)nl * n * n / 100) / n));
-            wa.arr_waste = std::max(8, wa.aug_waste / 3);          // (a full-row bid with its cache refresh: three sweeps)
-            if (CYTO_KNOB("CYTO_ARR_WASTE").set) wa.arr_waste = std::max(1, CYTO_KNOB("CYTO_ARR_WASTE").value);     // (developer knob, read once per process: tools/batch_chunks_bench.py)
-            wa.seg_quorum = nl > 1 ? std::max(1, nl / 4) : 0;
-            wa.seg_sync = nullptr;
-            wa.same_prev = (j.h_ngroups < n && n >= 2) ? j.b_same.as<int32_t>() : nullptr;
-            wa.sc = j.b_wide.as<char>() + sc_off;
-            CYTO_HIP(hipMemsetAsync(wa.sc, 0, WIDE_SC_BYTES, stream));
-            wa.scx = j.b_wide.as<char>() + scx_off;
-            CYTO_HIP(hipMemsetAsync(wa.scx, 0, wide_sc_ext_bytes(n), stream));
-            CYTO_HIP(hipMemsetAsync(wa.scx, 0xFF, wide_sc_ones_bytes(n), stream));     // (the machine's bid words and lowest-bid arrays)
-            wa.par_groups = parg; wa.par = nullptr;
-            if (parg > 0) {
-                const size_t np_ = ((size_t)n + 63) & ~(size_t)63;
-                wa.par = j.b_wide.as<char>() + par_off;
-                CYTO_HIP(hipMemsetAsync(wa.par, 0, 256, stream));                                            // the control block ...
-                const int p_init[2] = {WIDE_PAR_GMAX + 1, WIDE_PAR_GMAX + 1};
-                CYTO_HIP(hipMemcpyAsync(wa.par + 8, p_init, sizeof p_init, hipMemcpyHostToDevice, stream));   // ... P[0], P[1]: "no conflict"
-                CYTO_HIP(hipMemsetAsync(wa.par + 256, 0xFF, (size_t)parg * np_ * 8, stream));                  // every search's labels: all-ones
-                CYTO_HIP(hipMemsetAsync(wa.par + 256 + (size_t)parg * np_ * 20, 0, np_ * 4, stream));          // the claim words
-                CYTO_HIP(hipStreamSynchronize(stream));                                                         // (p_init is a local)
-            }
-            wa.mc_groups = mcg; wa.gbmin = nullptr; wa.gdirty = nullptr; wa.gasg = nullptr; wa.gdense = nullptr; wa.ctl = nullptr;
-            if (mcg > 0) {
-                const size_t nblk = ((size_t)n + 63) / 64, nw32 = ((size_t)n + 31) / 32;
-                char *base = j.b_wide.as<char>() + ((2 * nT + 255) / 256) * 256;
-                wa.gbmin = reinterpret_cast<unsigned long long *>(base);          // nblk records of 128 bytes: [0] block minimum, [1] dirty bits
-                wa.gasg = reinterpret_cast<uint32_t *>(base + nblk * 128);
-                wa.gdense = wa.gasg + nw32; wa.gdirty = nullptr;
-                wa.ctl = base + wide_mc_state_bytes(n) - 256;
-                CYTO_HIP(hipMemsetAsync(wa.gbmin, 0, nblk * 128 + 2 * nw32 * 4, stream));
-                CYTO_HIP(hipMemset2DAsync(wa.gbmin, 128, 0xFF, 8, nblk, stream));   // the block minima: all-ones
-                CYTO_HIP(hipMemsetAsync(wa.ctl, 0, 256, stream));
-            }
-            // the post-column-reduction prices: snapshot for the reduction transfer AND the raw cost of every owner entry
-            CYTO_HIP(hipMemcpyAsync(wa.cassign, wa.v, nT, hipMemcpyDeviceToDevice, stream));
-            CYTO_HIP(hipMemsetAsync(wa.label, 0xFF, 2 * nT, stream));
-            CYTO_HIP(hipMemsetAsync(wa.bid, 0xFF, 2 * nT, stream));
-        }
-        DevBuf d_wa, d_sync;
-        if ((rc = d_wa.alloc(sizeof(WideArgs) * nl, stream)) || (rc = d_sync.alloc(sizeof(int32_t) * ((size_t)nl + 1), stream))) return rc;
-        for (WideArgs &wa : h_wa) wa.seg_sync = d_sync.as<int32_t>();
-        CYTO_HIP(hipMemcpyAsync(d_wa.p, h_wa.data(), sizeof(WideArgs) * nl, hipMemcpyHostToDevice, stream));
-        if ((rc = wide_launch_rt(d_wa.as<WideArgs>(), nl, n, stream))) return rc;
-        std::vector<int32_t> h_sync((size_t)nl + 1, 1);
-        std::vector<char> caches_fresh((size_t)nl, 0);            // (wide_arr's word: hardly a full-row bid -- no rebuild before the searches)
-        using BuildFn = decltype(build_caches);
-        auto rebuild_tramp = +[](void *ctx, const int32_t *flags) -> int { return (*static_cast<BuildFn *>(ctx))(reinterpret_cast<const int *>(flags)); };
-        for (int pass = 0;; pass++) {                              // the row-reduction rounds (they pause when the caches have gone stale)
-            if (pass && (rc = build_caches(h_sync.data() + 1))) return rc;
-            CYTO_HIP(hipMemsetAsync(d_sync.p, 0, sizeof(int32_t), stream));
-            if ((rc = wide_launch_arr(d_wa.as<WideArgs>(), nl, n, stream, pl.wide_wipe, pass > 0, d_sync.as<int32_t>(), rebuild_tramp, &build_caches, nl == 1 ? &h_wa[0] : nullptr))) return rc;
-            if (h_wa[0].aug_seg != 0) break;                       // (no pauses asked for: nothing to wait for)
-            CYTO_HIP(hipMemcpyAsync(h_sync.data(), d_sync.p, sizeof(int32_t) * ((size_t)nl + 1), hipMemcpyDeviceToHost, stream));
-            CYTO_HIP(hipStreamSynchronize(stream));
-            bool done = true;
-            for (int k = 0; k < nl; k++) { done = done && (h_sync[(size_t)k + 1] & 1) == 0; caches_fresh[(size_t)k] = (h_sync[(size_t)k + 1] & 2) != 0; h_sync[(size_t)k + 1] &= 1; }
-            if (done) break;
-        }
-        // the searches, in as many launches as they ask for: wide_aug returns when its row caches have gone stale (lap_wide.hip) and
-        // the whole chip rebuilds them against the prices reached -- only for the problems that still have searches to run
-        for (int pass = 0;; pass++) {
-            if (pass == 0) {
-                std::vector<int> need((size_t)nl);
-                for (int k = 0; k < nl; k++) need[(size_t)k] = caches_fresh[(size_t)k] ? 0 : 1;
-                if ((rc = build_caches(need.data()))) return rc;
-            } else if ((rc = build_caches(reinterpret_cast<const int *>(h_sync.data() + 1)))) return rc;
-            if (pass == 0) CYTO_HIP(hipEventRecord(ev_arr_done, stream));   // (ms_aug: the search kernel -- and what later passes add)
-            if (pass == 0 && h_wa[0].mc_groups == 0 && h_wa[0].par_groups == 0) {
-                // repeated spot rows (CytoSPACE's slots): their one-edge searches all at once, before the search kernel
-                bool dup = false;
-                for (int k = 0; k < nl; k++) dup = dup || h_wa[(size_t)k].same_prev != nullptr;
-                if (dup && (rc = wide_launch_claims(d_wa.as<WideArgs>(), nl, n, stream, d_sync.as<int32_t>()))) return rc;
-            }
-            CYTO_HIP(hipMemsetAsync(d_sync.p, 0, sizeof(int32_t), stream));
-            if ((rc = wide_launch_aug(d_wa.as<WideArgs>(), nl, n, stream, h_wa[0].mc_groups, h_wa[0].par_groups))) return rc;
-            if (h_wa[0].mc_groups > 0 || h_wa[0].par_groups > 0) { CYTO_HIP(hipStreamSynchronize(stream)); break; }
-            CYTO_HIP(hipMemcpyAsync(h_sync.data(), d_sync.p, sizeof(int32_t) * ((size_t)nl + 1), hipMemcpyDeviceToHost, stream));
-            CYTO_HIP(hipStreamSynchronize(stream));                // (d_wa is read by the kernels until here)
-            bool done = true;
-            for (int k = 0; k < nl; k++) done = done && h_sync[(size_t)k + 1] == 0;
-            if (done) break;
-        }
-        return CYTO_OK;
-    }
     if ((rc = set_max_dynamic_lds(reinterpret_cast<const void *>(kern)))) return rc;
     if (pl.shm_chain > (size_t)LDS_DYNAMIC_MAX || shm_aug > (size_t)LDS_DYNAMIC_MAX || shm_lazy > (size_t)LDS_DYNAMIC_MAX) return CYTO_ERR_INTERNAL;
     hipLaunchKernelGGL(kern, dim3(nl), dim3(BLOCK2), pl.shm_chain, stream, d_c2.as<Chain2Args>());
@@ -3605,7 +3290,7 @@ static int launch_batch(const F32Plan &pl, std::vector<F32Job> &jobs, hipStream_
     if (!pl.lazy) return launch_dense(d_c2.as<Chain2Args>(), nl);
 
     // fresh caches (floors against the prices the augmentation starts from), then the cache-certified search
-    if ((rc = build_caches(nullptr))) return rc;
+    if ((rc = build_all_caches())) return rc;
     void (*lk)(const LazyArgs *) = pl.lz_lds_state ? jv_aug_lazy<true> : (pl.lz_cs_lds ? jv_aug_lazy<false, true> : jv_aug_lazy<false>);
     if ((rc = set_max_dynamic_lds(reinterpret_cast<const void *>(lk)))) return rc;
     hipLaunchKernelGGL(lk, dim3(nl), dim3(BLOCK2), shm_lazy, stream, d_la.as<LazyArgs>());
@@ -3655,7 +3340,6 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
     pl.rowblocks = max(1, min(pl.rowblocks, (n + 15) / 16));
     pl.rows_per_block = (n + pl.rowblocks - 1) / pl.rowblocks;
     pl.rowblocks = (n + pl.rows_per_block - 1) / pl.rows_per_block;
-    pl.cache_grid = max(1, min(n, 1024));
     // (measured, tools/cache_build_bench.py, gpurun_out/r04v: n = 20 000: 8 waves per CU x 8 quads in flight 0.404 ms = 3.96 TB/s, 50 000:
     //  2.13 ms = 4.69 TB/s -- the workgroup-per-row builders 0.750 / 3.27 ms; n = 10 000: 32 x 4 0.126 ms, 8 x 8 0.137, old 0.183:
     //  with few rows per wave the second sweep of a wave's first row, from L2, costs less than the waves it would take away)
@@ -3665,15 +3349,14 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
     //  5 % of the best setting of every instance measured (uniform 20 000: 0.412 ms, 50 000: 2.25 ms, 10 000: 0.123 ms).
     //  n = 50 000 prefers 8 waves per CU by more than the build's own time (same box, gpurun_out/r04z: row reduction 21.5-23.0 ms after a
     //  build with 8 waves, 24.0-24.8 ms after one with 20 -- 183 instead of 146 full-row bids, each holding up a round for one 200-KB sweep).
-    pl.cache_unroll = 8;
-    pl.cache_waves = n > 32768 ? 8 : 20;
-    if (CYTO_KNOB("CYTO_CACHE_KEEP").set) pl.cache_keep = std::max(0, std::min(63, CYTO_KNOB("CYTO_CACHE_KEEP").value));     // (developer knob)
-    // (cyto_lap_opts.cache_waves / cache_unroll / cache_stream -- tools/cache_build_bench.py and the builder tests: -1 waves selects the
-    //  workgroup-per-row builders)
-    if (opts.cache_waves != 0) pl.cache_waves = opts.cache_waves < 0 ? 0 : opts.cache_waves;
-    if (opts.cache_unroll != 0) pl.cache_unroll = opts.cache_unroll;
-    if (opts.cache_stream != 0) pl.cache_stream = opts.cache_stream > 0 ? 1 : 0;
-    pl.cus = device_cus(device_id);
+    pl.cache.unroll = 8;
+    pl.cache.waves = n > 32768 ? 8 : 20;
+    // (cyto_lap_opts.cache_waves / cache_unroll / cache_stream -- tools/cache_build_bench.py and the builder tests; cache_waves = -1,
+    //  which selected the round-3 builders, is the default now)
+    if (opts.cache_waves > 0) pl.cache.waves = opts.cache_waves;
+    if (opts.cache_unroll != 0) pl.cache.unroll = opts.cache_unroll;
+    if (opts.cache_stream != 0) pl.cache.stream = opts.cache_stream > 0 ? 1 : 0;
+    pl.cache.cus = device_cus(device_id);
     const int per2 = 4 * BLOCK2;
     // which chain variant: by size, or the large-n variants forced at a small n (opts.chain_variant; the test-suite
     // runs them on instances the CPU oracle solves in a second)
@@ -3682,11 +3365,6 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
     const bool chain_opts = opts.chain_variant || opts.augmentation || opts.no_handover || opts.inject_exceptions ||
                             opts.group_state_global || opts.aux_state_global;
     pl.wide = opts.mode == 2 || (opts.mode == 0 && !chain_opts);
-    pl.wide_rounds = opts.wide_rounds < 0 ? 0 : (opts.wide_rounds > 0 ? opts.wide_rounds : 4096 + (long long)n / 4);
-    pl.wide_groups = opts.wide_groups;
-    pl.wide_rebuild = opts.wide_rebuild;
-    pl.wide_wipe = opts.wide_wipe;
-    pl.wide_par = opts.wide_par;
     pl.force_l2 = opts.chain_variant != 0;
     pl.no_cs_lds = opts.chain_variant == 3;            // (3: as 2, with colsol in global memory too -- what n > 65 535 uses)
     pl.lds_variant = !pl.force_l2 && n <= 13 * per2;
@@ -3798,10 +3476,11 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
     CYTO_HIP(hipStreamSynchronize(stream));
     CYTO_HIP(hipEventRecord(e1b, stream));
 
-    // ---- stage 2: per-problem argument blocks ----
+    // ---- stage 2: per-problem argument blocks of the chain solver ----
     for (F32Job &j : jobs) {
         if (!j.alive()) continue;
         if (j.h_nonfinite) { j.status = CYTO_ERR_NONFINITE; continue; }
+        if (pl.wide) continue;
         float *d_v = j.b_fws.as<float>(), *d_u = d_v + n;
         int32_t *d_rowsol = j.b_iws.as<int32_t>(), *d_colsol = d_rowsol + n, *d_free = d_rowsol + 3 * (size_t)n;
         const int ng = j.h_ngroups;
@@ -3811,7 +3490,7 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
         // duplicate-row skip: per-group state in LDS when it fits beside v (4 B) and colsol (2 B) per column
         c2.rowgid = j.b_gid.as<int32_t>(); c2.ngroups = ng; c2.gmode = 0; c2.g_hbest = nullptr; c2.g_hstamp = nullptr;
         c2.auxlds = 0; c2.aug_start = 0;
-        c2.rowmap = j.rowmap_host ? j.b_rowmap.as<int32_t>() : nullptr;
+        c2.rowmap = j.rowmap();
         LazyArgs &la = j.la;
         memset(&la, 0, sizeof la);
         j.shm_lazy = pl.lz_base_shm;
@@ -3822,7 +3501,7 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
             la.srow = d_rowsol + 6 * (int64_t)n;      // [n+1]: runs into the next slot, which the lazy path does not use
             la.slist = d_rowsol + 8 * (int64_t)n; la.slevel = d_rowsol + 9 * (int64_t)n;
             la.rowgid = j.b_gid.as<int32_t>(); la.cache_col = j.b_ccol.as<uint32_t>(); la.cache_val = j.b_cval.as<float>();
-            la.rowmap = j.rowmap_host ? j.b_rowmap.as<int32_t>() : nullptr;
+            la.rowmap = j.rowmap();
             la.misc = j.b_misc.as<char>(); la.ngroups = ng; la.gmode = 0; la.g_hbest = nullptr; la.g_hstamp = nullptr;
             la.may_bail = opts.no_handover ? 0 : 1;   // (launch_batch clears it where no dense kernel can take over)
             la.debug_exc = opts.inject_exceptions;
@@ -3853,9 +3532,18 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
         j.shm_aug = base_aug + (c2.auxlds ? (size_t)npad * 6 : 0) + 32;
     }
 
-    // ---- stage 3: the chains, one launch per phase for the whole batch ----
+    // ---- stage 3: the solver, one launch per phase for the whole batch ----
     DevBuf d_c2, d_la;
-    if (opts.chain_variant >= 2) rc = launch_batch<0, false>(pl, jobs, stream, e1c, e1d, d_c2, d_la);
+    if (pl.wide) {
+        const WidePlan wp = {n, opts.wide_rounds < 0 ? 0 : (opts.wide_rounds > 0 ? opts.wide_rounds : 4096 + (long long)n / 4),
+                             opts.wide_rebuild, opts.wide_wipe, opts.wide_par, pl.cache};
+        std::vector<WideJob> wj;
+        for (F32Job &j : jobs)
+            if (j.alive())
+                wj.push_back({j.dcost, j.dld, j.rowmap(), j.b_fws.as<float>(), j.b_iws.as<int32_t>(), j.b_ccol.as<uint32_t>(),
+                              j.b_cval.as<float>(), j.b_misc.as<char>(), j.same(n), j.h_ngroups, &j.b_wide});
+        rc = wide_solve_batch(wp, wj, stream, e1c, e1d);
+    } else if (opts.chain_variant >= 2) rc = launch_batch<0, false>(pl, jobs, stream, e1c, e1d, d_c2, d_la);
     else if (pl.force_l2 && n <= 5 * per2) rc = launch_batch<5, false>(pl, jobs, stream, e1c, e1d, d_c2, d_la);
     else if (pl.force_l2 && n <= 16 * per2) rc = launch_batch<16, false>(pl, jobs, stream, e1c, e1d, d_c2, d_la);
     else if (pl.force_l2) rc = launch_batch<0, false>(pl, jobs, stream, e1c, e1d, d_c2, d_la);
@@ -3891,9 +3579,8 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
             // the float64 certificate (above): one more streaming pass, on the stream, behind the solve
             DevBuf b_viol;
             if ((rc = b_viol.alloc(((size_t)n + 4) * sizeof(double), stream))) return rc;
-            const int g = std::max(1, std::min((n + 3) / 4, pl.cus * 8));
-            hipLaunchKernelGGL(dual_gap_rows, dim3(g), dim3(256), 0, stream, n, j.dld, j.dcost, j.rowmap_host ? j.b_rowmap.as<int32_t>() : (const int32_t *)nullptr,
-                               d_rowsol, d_v, b_viol.as<double>());
+            const int g = std::max(1, std::min((n + 3) / 4, pl.cache.cus * 8));
+            hipLaunchKernelGGL(dual_gap_rows, dim3(g), dim3(256), 0, stream, n, j.dld, j.dcost, j.rowmap(), d_rowsol, d_v, b_viol.as<double>());
             hipLaunchKernelGGL(dual_gap_finish, dim3(1), dim3(1024), 0, stream, n, b_viol.as<double>(), b_viol.as<double>() + n);
             CYTO_HIP(hipGetLastError());
             CYTO_HIP(hipMemcpyAsync(h_gap, b_viol.as<double>() + n, sizeof h_gap, hipMemcpyDeviceToHost, stream));
@@ -3926,7 +3613,7 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
             info->aug_dense_scans = h_counters[C2_AUG_DENSE];
             info->aug_sparse_inits = h_counters[C2_AUG_SPARSE_INIT];
             info->aug_handover = -1;
-            if (pl.lazy) {
+            if (pl.lazy && !pl.wide) {
                 int h[3] = {0, 0, 0};
                 CYTO_HIP(hipMemcpy(h, j.b_misc.as<char>() + 128, sizeof h, hipMemcpyDeviceToHost));
                 if (h[2] < h[0]) info->aug_handover = h[2];
@@ -3942,7 +3629,6 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
                 info->wide_rounds = wc[WC_ROUNDS]; info->wide_retired = wc[WC_RETIRED]; info->wide_dense_arr = wc[WC_DENSE_ARR];
                 info->wide_dense_aug = wc[WC_DENSE_AUG]; info->wide_aug_rounds = wc[WC_AUG_ROUNDS]; info->wide_aug_settled = wc[WC_AUG_PROCESSED];
                 info->wide_trivial = wc[WC_TRIVIAL]; info->wide_verify_passes = wc[WC_VERIFY_PASSES]; info->wide_aug_launches = wc[WC_AUG_LAUNCHES];
-                info->aug_handover = -1;
                 {   // phase timers the wide kernels keep (100 MHz ticks at misc + 256): diagnostics for tools/wide_large.py
                     long long dbg[16] = {0};
                     CYTO_HIP(hipMemcpy(dbg, j.b_misc.as<char>() + 256, sizeof dbg, hipMemcpyDeviceToHost));
@@ -4280,40 +3966,6 @@ int cyto_lap_f64(int n, const double *cost, int64_t ld, int cost_on_device, int3
                  double *u, double *v, double *total, cyto_lap_info *info, int device_id, void *stream) {
     return cyto::lap_solve_f64(n, cost, ld, cost_on_device, rowsol, colsol, u, v, total, info, device_id, reinterpret_cast<hipStream_t>(stream), cyto::k_default_opts);
 }
-
-#ifdef CYTO_ARR_PROF
-// profiling build only (tools/prof_arr_step.py): the step-cycle accumulators of the last jv_chain2 launch
-int cyto_arr_prof_read(long long *out16) {
-    CYTO_HIP(hipMemcpyFromSymbol(out16, HIP_SYMBOL(cyto::g_arr_prof), sizeof(long long) * 16));
-    return CYTO_OK;
-}
-#endif
-
-#ifdef LZ_PROF
-// profiling build only (tools/prof_lazy_step.py): the step-cycle accumulators of the last jv_aug_lazy launch
-int cyto_lz_prof_read(long long *out24) {
-    CYTO_HIP(hipMemcpyFromSymbol(out24, HIP_SYMBOL(cyto::g_lz_prof), sizeof(long long) * 24));
-    return CYTO_OK;
-}
-#endif
-
-#ifdef CYTO_AUG_TRACE
-// debugging build only (tools/trace_aug_scans.py): cumulative scans / elided scans after every search of the last jv_aug2 launch
-int cyto_aug_trace_read(long long *out, int count) {
-    CYTO_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(cyto::g_aug_trace), sizeof(long long) * 2 * (size_t)count));
-    return CYTO_OK;
-}
-#endif
-
-#ifdef CYTO_AUG_PROF
-// profiling build only (tools/prof_aug_step.py): read and clear the step-cycle accumulators of the dense augmentation
-int cyto_aug_prof_read(long long *out16) {
-    long long z[16] = {0};
-    CYTO_HIP(hipMemcpyFromSymbol(out16, HIP_SYMBOL(cyto::g_aug_prof), sizeof z));
-    CYTO_HIP(hipMemcpyToSymbol(HIP_SYMBOL(cyto::g_aug_prof), z, sizeof z));
-    return CYTO_OK;
-}
-#endif
 
 int cyto_lap_f32_rowmap(int n, const float *cost_rows, int64_t ld, int nu, int cost_on_device, const int32_t *rowmap,
                         int32_t *rowsol, int32_t *colsol, float *u, float *v, double *total, cyto_lap_info *info, int device_id,

@@ -28,18 +28,56 @@
 //              converged; rows that fail are relaxed from their full cost row and the search continues).  PAR: the searches of
 //              16 consecutive free rows of ONE problem at once, a workgroup each, the conflict-free prefix committed in row order.
 //
-// Row caches: lap_jv.hip (build_row_caches) -- <= 63 columns per row with their raw costs, sorted by column, and a floor
+// Row caches: lap_jv.hip (build_caches) -- <= 63 columns per row with their raw costs, sorted by column, and a floor
 // that bounds the reduced cost of every other column for as long as prices only decrease (they do: the price update of
 // this mode is clamped).
 #include "lap_dev.h"
 #include "lap_wide.h"
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <mutex>
 #include <thread>
 #include <vector>
 
 namespace cyto {
+
+// One problem of a batch: the kernels' argument block.  Every pointer is device memory; the work arrays are the driver's (WideJob).
+//   v, u, cassign   [n] prices, row duals (written at the end), c[colsol[j]][j] per column
+//   label           [n] 64-bit search labels (ordered distance << 32 | tight-hop count << 20 | predecessor row); all-ones between searches
+//   bid             [n] 64-bit bids of a row-reduction round (ordered price << 32 | row); all-ones between rounds
+//   rowsol, colsol  [n] (-1 = free / unassigned), matches [n] columns claimed per row by the column reduction
+//   act0, act1      [n] active-row lists of the row-reduction rounds;  freerows [n];  touched [n] columns labelled in a search
+//   slot_j, slot_p, slot_c  [n] per active slot: the bid's column (-1 = retired), price, raw cost of that entry
+//   cache_col/val   [n][64] row caches (lap_jv.hip: build_caches)
+//   misc            512 bytes: +4 status, +8 double total, +16 long long counters[] (lap_jv.hip indices), +160.. wide counters,
+//                   +256 phase timers ([12]: launches of wide_arr, [13] scaled?, [14] phases begun), +384 what the phase machine of the row reduction leaves for wide_arr
+//   same_prev       [n] 1 = the row equals the row before it (runs of identical rows: CytoSPACE repeats a spot's row per slot), or null
+//   seg_sync        shared by the launch, or null: [0] workgroups that asked for fresh caches (zeroed by the driver before every launch
+//                   of wide_arr / wide_aug), [1 + b] wide_arr: 1 = problem b's rounds paused; wide_aug: searches problem b still has to run
+//   sc              2 KB, zeroed by the driver: the control block of the row-reduction phase machine (ScCtl)
+//   scx             the phase machine's own arrays (wide_sc_ext_bytes(n), 256-byte aligned; the first wide_sc_ones_bytes(n) all-ones, the rest zero):
+//                   ScMem
+//   par_groups, par searches of one problem that run at once on as many workgroups (0 / 1: one at a time) and their state (ParCtl)
+//   arr_waste       wide_arr: full-row bids (with their cache refresh) of one launch after which the list rounds pause (aug_seg == 0)
+//   aug_seg         when a launch of wide_aug returns to the driver for fresh row caches: -1 never, k > 0 after k searches, 0 when
+//                   its full-row relaxations reach aug_waste or seg_quorum workgroups of the launch have asked (misc + 132 holds the
+//                   number of searches done)
+// (fields through an X-macro: the kernels read the block through a mirror struct whose pointers are typed as GLOBAL, so that
+//  every access is a global_* instruction -- through pointers loaded from memory it would be a FLAT one, and flat accesses
+//  also count on lgkmcnt: every LDS wait would wait for the outstanding global loads too)
+#define WIDE_FIELDS(P, S)                                                                                                  \
+    S(int, n) S(int64_t, ld) P(const float, cost) P(const int32_t, rowmap) P(float, v) P(float, u) P(float, cassign)          \
+    P(unsigned long long, label) P(unsigned long long, bid) P(int32_t, rowsol) P(int32_t, colsol) P(int32_t, matches)          \
+    P(int32_t, freerows) P(int32_t, act0) P(int32_t, act1) P(int32_t, touched) P(int32_t, slot_j) P(float, slot_p)            \
+    P(float, slot_c) P(uint32_t, cache_col) P(float, cache_val) P(char, misc) S(long long, max_rounds)                     \
+    P(const int32_t, same_prev) P(int32_t, seg_sync) S(int, aug_seg) S(int, aug_waste) S(int, arr_waste) S(int, seg_quorum)   \
+    P(char, sc) S(int, par_groups) P(char, par) P(char, scx)
+#define WIDE_F_PTR(T, name) T *name;
+#define WIDE_F_VAL(T, name) T name;
+struct WideArgs { WIDE_FIELDS(WIDE_F_PTR, WIDE_F_VAL) };
+
+constexpr size_t WIDE_SC_BYTES = 2048;
 
 namespace {
 
@@ -1247,7 +1285,6 @@ size_t wide_aug_lds_bytes(int n, bool vlds, bool clds) {
 }
 bool wide_aug_vlds(int n) { return n <= 65534 && wide_aug_lds_bytes(n, true, true) + 4096 <= (size_t)LDS_DYNAMIC_MAX; }
 bool wide_aug_clds(int n) { return n <= 65534 && wide_aug_lds_bytes(n, false, true) + 4096 <= (size_t)LDS_DYNAMIC_MAX; }
-size_t wide_aug_lds_bytes(int n) { return wide_aug_lds_bytes(n, wide_aug_vlds(n), wide_aug_clds(n)); }
 
 struct AugShared {
     unsigned long long T;          // best unassigned column: (ordered distance << 32 | tight hops << 20 | column)
@@ -1287,7 +1324,7 @@ struct ParCtl {
 };
 static_assert(sizeof(ParCtl) <= 256, "control block");
 constexpr int PAR_GMAX = 64;
-size_t wide_par_state_bytes(int n, int G) {
+static size_t wide_par_state_bytes(int n, int G) {
     const size_t np = ((size_t)n + 63) & ~(size_t)63;
     // control block | labels G x n | touched G x n | hops G x 2n | claim n | price log (col, val) | owner log (col, owner)
     return 256 + (size_t)G * np * 8 + (size_t)G * np * 4 + (size_t)G * np * 8 + np * 4 + np * 8 + np * 8;
@@ -1855,9 +1892,6 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
             commit = active && have && g < Pb;
             if (active && !commit) c_discarded++;
         }
-#ifdef CYTO_AUG_FIN_SPLIT                                        // (developer build: the finish by parts -- the wait for the batch's slowest search, the
-        AUG_LAP(t_verify)                                        //  claims and the conflict check go into the certificate timer, ...
-#endif
         if (commit) {
             int myscans = 0;
             for (int q = tid; q < nt; q += WT) {
@@ -1904,9 +1938,6 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
             atomicAnd(&dirty[k >> 5], ~(1u << (k & 31)));
             bmin[k >> 6] = ~0ull;
         }
-#ifdef CYTO_AUG_FIN_SPLIT                                        //  ... update + flip stay, reset + logs + the batch's last barrier into the one-edge timer)
-        AUG_LAP(t_finish)
-#endif
         // (keeping the dense bits across searches was measured: fewer rounds, but more full-row relaxations -- slower)
         if (s.anydense) for (int q = tid; q < nw32; q += WT) dense[q] = 0;
         __syncthreads();
@@ -1930,11 +1961,7 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
             if (Pb < 1) perr = 1;
             batchno++; c_batches++;
         }
-#ifdef CYTO_AUG_FIN_SPLIT
-        AUG_LAP(t_triv)
-#else
         AUG_LAP(t_finish)
-#endif
     }
 
     // ---- duals, total, counters ----
@@ -1990,389 +2017,6 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
         long long *dbg = reinterpret_cast<long long *>(a.misc + 256);      // (100 MHz ticks)
         dbg[8] += t_rounds; dbg[9] += t_verify; dbg[10] += t_finish; dbg[11] += t_triv;
         if (PAR) { dbg[15] = ld_sc1(reinterpret_cast<unsigned long long *>(&pc->c_batches)); dbg[7] = ld_sc1(reinterpret_cast<unsigned long long *>(&pc->c_discarded)); }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// AUGMENTATION on SEVERAL workgroups (one problem): the same searches, the same labels -- the fixed point of §"AUGMENTATION"
-// above does not care who relaxes what when -- with the search state in global memory (L2) instead of LDS and NO barrier
-// inside a search's steady state: every wave of every workgroup loops on its own { take the best dirty columns of the blocks
-// it owns, settle them, rebuild those blocks' minima }.  Exchange is by agent-scope atomics only (labels, dirty bits, block
-// minima, best unassigned column); everything mutable is read with sc1 loads and written with sc1 stores / atomics.
-//   * block minimum rebuilt without losing a concurrent update: the owner stores all-ones, WAITS, reads the block's dirty bits
-//     and labels, then atomic-mins what it found; an updater completes its label atomic, then its dirty bit (waits), then
-//     atomic-mins the block minimum -- whichever way they interleave, the owner either sees the dirty column or the
-//     updater's atomic min lands after the owner's store;
-//   * settling: dirty bit cleared, WAIT, label read -- an update in between sets the bit again;
-//   * termination: a wave without work leaves the `active` count and polls; all waves idle -> grid barrier -> did anyone
-//     settle anything since the last barrier?  No: converged (nothing can appear while nobody runs).  Yes: once more.
-// Grid barriers (a monotonic arrival counter, bounded spins) separate only the phases of a search: root, rounds, certificate
-// pass, price update + path flip, reset.  Workgroups 0, 8, 16 ... of the launch take part (observed: block b runs on XCD b % 8,
-// so they share one L2 -- a speed matter only, nothing here depends on placement).
-// ------------------------------------------------------------------------------------------------------------------
-struct McCtl {
-    unsigned long long T;
-    int ntouch, active, progress[2], fail, doroot, rootdense, anydense, f, err, scans;
-    unsigned int bar_arrive, bar_gen;
-    int pad_;
-    long long c_relax, c_hops, c_macro, c_proc, c_dense, c_trivial, c_verify;
-};
-static_assert(sizeof(McCtl) <= 256, "control block");
-
-// per 64-column block ONE 128-byte record (its own cache line: the block minimum and the dirty bits take atomics from every
-// workgroup, and atomics to one line serialise): [0] smallest dirty label, [1] dirty bits
-constexpr int MC_REC = 16;             // 64-bit words per record
-size_t wide_mc_state_bytes(int n) {
-    const size_t nblk = ((size_t)n + 63) / 64, nw32 = ((size_t)n + 31) / 32;
-    return ((nblk * 128 + 2 * nw32 * 4 + 255) / 256) * 256 + 256;
-}
-int wide_mc_groups(int nb, int n) {
-    // Measured (round 3, tools/wide_large.py --groups G): on uniform instances the one-workgroup kernel is faster (n = 20 000: 39 ms
-    // against 46 ms with 4-8 groups, 55 ms with 16) -- 4-8x the waves settle 1.8-2.6x the columns (speculation further from the
-    // frontier) and every exchange is a global atomic instead of an LDS one; on few-cell-type chunks, where full-row relaxations
-    // dominate, 8 groups are 1.4x faster (10 000-cell chunk: 2.55 -> 1.79 s).  So: on request only (cyto_lap_opts.wide_groups).
-    (void)nb; (void)n;
-    return 0;
-}
-
-#define MC_WAIT_VM() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-
-__device__ __forceinline__ void mc_barrier(McCtl *c, int G, unsigned &gen) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        MC_WAIT_VM();
-        const unsigned arrived = atomicAdd(&c->bar_arrive, 1u) + 1u;
-        if (arrived == (gen + 1u) * (unsigned)G) st_sc1(&c->bar_gen, gen + 1u);
-        else {
-            long long spins = 0;
-            while (ld_sc1(&c->bar_gen) <= gen) {
-                __builtin_amdgcn_s_sleep(4);
-                if (++spins > (1ll << 25)) { atomicExch(&c->err, 2); break; }      // (a lost workgroup must not hang the device)
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
-    gen++;
-    __syncthreads();
-}
-
-__global__ __launch_bounds__(WT) void wide_aug_mc(const WideArgs *__restrict__ batch) {
-    if (blockIdx.x & 7) return;
-    const int g = uni((int)(blockIdx.x >> 3));
-    const WideArgs a = load_wide_args(batch, 0);
-    const int G = a.mc_groups;
-    McCtl *c = reinterpret_cast<McCtl *>(a.ctl);
-    const int n = a.n, tid = threadIdx.x, lane = tid & 63, w = uni((int)(threadIdx.x >> 6));
-    const int gw = g * WNW + w, W = G * WNW, gtid = g * WT + tid, GT = G * WT;
-    const int nblk = (n + 63) / 64, nw32 = (n + 31) / 32;
-    const int numfree = *reinterpret_cast<const int *>(a.misc + 128);
-    unsigned gen = 0;
-    __shared__ double s_tot[WNW];
-    // assigned bits (block minima, dirty and dense bits, the control block: initialised by the host)
-    for (int c0 = gw * 64; c0 < nw32 * 32; c0 += W * 64) {
-        const int cc = c0 + lane;
-        const uint64_t m = __ballot(cc < n && a.colsol[cc] >= 0);
-        if (lane == 0) { st_sc1(a.gasg + (c0 >> 5), (uint32_t)m); if ((c0 >> 5) + 1 < nw32) st_sc1(a.gasg + (c0 >> 5) + 1, (uint32_t)(m >> 32)); }
-    }
-    if (gtid == 0) st_sc1(&c->T, ~0ull);
-    mc_barrier(c, G, gen);
-
-    auto is_asg = [&](int col) -> bool { return (ld_sc1(a.gasg + (col >> 5)) >> (col & 31)) & 1u; };
-    auto is_dense = [&](int i) -> bool { return (ld_sc1(a.gdense + (i >> 5)) >> (i & 31)) & 1u; };
-    auto offer = [&](int col, unsigned long long lv, int row) -> unsigned long long {
-        return atomicMin(a.label + col, lkey(lv, (uint32_t)row));
-    };
-    auto after_offer = [&](int col, unsigned long long lv, int row, unsigned long long old) {
-        const unsigned long long key = lkey(lv, (uint32_t)row);
-        if (key < old) {
-            if (old == ~0ull) st_sc1(a.touched + atomicAdd(&c->ntouch, 1), col);
-            if (lv_of(old) > lv) {                              // the label value itself dropped (not only the row of a tie)
-                const unsigned long long ck = lkey(lv, (uint32_t)col);
-                if (is_asg(col)) {
-                    atomicOr(a.gbmin + (int64_t)(col >> 6) * MC_REC + 1, 1ull << (col & 63));
-                    MC_WAIT_VM();                                   // the dirty bit is in place before the block minimum says so
-                    atomicMin(a.gbmin + (int64_t)(col >> 6) * MC_REC, ck);
-                } else atomicMin(&c->T, ck);
-            }
-        }
-    };
-    auto relax_to = [&](int col, unsigned long long lv, int row) { after_offer(col, lv, row, offer(col, lv, row)); };
-
-    long long c_proc = 0, c_dense = 0, c_trivial = 0, c_hops = 0, c_macro = 0, c_verify = 0;
-    int f = 0, par = 0;
-    for (;;) {
-        // ---- searches that end at the free row's own best column: workgroup 0, wave 0 ----
-        if (g == 0 && w == 0) {
-            while (f < numfree) {
-                const int fr = a.freerows[f];
-                const uint32_t col = a.cache_col[(int64_t)fr * KC + lane];
-                const float val = a.cache_val[(int64_t)fr * KC + lane];
-                const float tau = rdlane(val, KCU);
-                const bool valid = lane < KCU && col != COLSENT;
-                const uint32_t od = valid ? f2ord(val - ld_sc1(a.v + (valid ? col : 0))) : 0xFFFFFFFFu;
-                const uint32_t omin = wave_min_u32(od);
-                const bool un = valid && od == omin && !is_asg((int)col);
-                const uint64_t mu = __ballot(un);
-                if (!(omin != 0xFFFFFFFFu && mu && tau > ord2f(omin))) break;
-                const int l = __ffsll((unsigned long long)mu) - 1;
-                if (lane == l) {
-                    st_sc1(a.rowsol + fr, (int32_t)col); st_sc1(a.colsol + col, (int32_t)fr); st_sc1(a.cassign + col, val);
-                    atomicOr(a.gasg + (col >> 5), 1u << (col & 31));
-                }
-                MC_WAIT_VM();
-                c_trivial++; c_hops++;
-                f++;
-            }
-            if (lane == 0) st_sc1(&c->f, f);
-        }
-        mc_barrier(c, G, gen);
-        f = uni(ld_sc1(&c->f));
-        if (f >= numfree || ld_sc1(&c->err)) break;
-        const int fr = a.freerows[f];
-        const float *__restrict__ frow = a.cost + wrow_off(a.rowmap, fr, a.ld);
-        const float ftau = a.cache_val[(int64_t)fr * KC + KCU];
-        if (g == 0 && w == 0) {                                    // root: d[j] = c[fr][j] - v[j] for the cached columns
-            const uint32_t col = a.cache_col[(int64_t)fr * KC + lane];
-            const float val = a.cache_val[(int64_t)fr * KC + lane];
-            if (lane < KCU && col != COLSENT) relax_to((int)col, (unsigned long long)f2ord(val - ld_sc1(a.v + col)) << 12, fr);
-        }
-        if (gtid == 0) { st_sc1(&c->active, W); st_sc1(&c->progress[par], 0); }
-        mc_barrier(c, G, gen);
-
-        for (;;) {
-            // ================= asynchronous rounds, until a whole macro round settles nothing =================
-            for (;;) {
-                bool counted = true, progressed = false;
-                long long idle = 0;
-                for (;;) {
-                    const unsigned long long Tlv = uni(lv_of(ld_sc1(&c->T)));
-                    unsigned long long mk = ~0ull;
-                    for (int b = gw + W * lane; b < nblk; b += W * 64) mk = umin64(mk, ld_sc1(a.gbmin + (int64_t)b * MC_REC));
-                    uint64_t pkey[AP];
-                    {
-#pragma unroll
-                        for (int q = 0; q < AP; q++) {
-                            const uint32_t dk = (uint32_t)(mk >> 32);
-                            const uint32_t m = wave_min_u32(dk);
-                            const uint32_t m2 = wave_min_u32(dk == m ? (uint32_t)mk : 0xFFFFFFFFu);
-                            pkey[q] = m == 0xFFFFFFFFu ? KEYMAX : (((uint64_t)m << 32) | m2);
-                            if (mk == pkey[q]) mk = ~0ull;
-                            if (lv_of(pkey[q]) >= Tlv) pkey[q] = KEYMAX;
-                        }
-                    }
-                    if (pkey[0] == KEYMAX) {                       // nothing to settle in this wave's blocks right now
-                        if (counted) { MC_WAIT_VM(); if (lane == 0) atomicSub(&c->active, 1); counted = false; }
-                        if (uni(ld_sc1(&c->active)) <= 0) break;
-                        __builtin_amdgcn_s_sleep(127);              // (hundreds of idle waves polling three words must not saturate their L2 channel)
-                        if (++idle > (1ll << 21)) { if (lane == 0) atomicExch(&c->err, 3); break; }
-                        continue;
-                    }
-                    if (!counted) { if (lane == 0) atomicAdd(&c->active, 1); counted = true; }
-                    if (!progressed) { if (lane == 0) st_sc1(&c->progress[par], 1); progressed = true; }
-                    bool pk[AP]; int pj[AP], oi[AP];
-                    unsigned long long lab[AP];
-                    float ca[AP], vp[AP], val[AP];
-                    uint32_t col[AP];
-#pragma unroll
-                    for (int q = 0; q < AP; q++) {
-                        pk[q] = pkey[q] != KEYMAX;
-                        pj[q] = (int)lid_of(pkey[q]);
-                        if (pk[q] && lane == 0) atomicAnd(a.gbmin + (int64_t)(pj[q] >> 6) * MC_REC + 1, ~(1ull << (pj[q] & 63)));
-                    }
-                    MC_WAIT_VM();                                   // the bits are cleared before the labels are read
-#pragma unroll
-                    for (int q = 0; q < AP; q++) {
-                        lab[q] = ~0ull; ca[q] = 0.0f; vp[q] = 0.0f; oi[q] = 0;
-                        if (pk[q]) { lab[q] = uni(ld_sc1(a.label + pj[q])); ca[q] = uni(ld_sc1(a.cassign + pj[q])); vp[q] = uni(ld_sc1(a.v + pj[q])); oi[q] = uni(ld_sc1(a.colsol + pj[q])); }
-                    }
-#pragma unroll
-                    for (int q = 0; q < AP; q++) {
-                        col[q] = COLSENT; val[q] = 0.0f;
-                        if (pk[q]) { col[q] = a.cache_col[(int64_t)oi[q] * KC + lane]; val[q] = a.cache_val[(int64_t)oi[q] * KC + lane]; }
-                    }
-                    unsigned long long old[AP], co[AP];
-                    bool off[AP], dn[AP];
-                    const unsigned long long Tnow = uni(lv_of(ld_sc1(&c->T)));
-#pragma unroll
-                    for (int q = 0; q < AP; q++) {
-                        off[q] = false; dn[q] = false; old[q] = 0; co[q] = 0;
-                        const uint32_t dord = (uint32_t)(lab[q] >> 32), kq = (uint32_t)(lab[q] >> 20) & LKMAX;
-                        if (pk[q] && lv_of(lab[q]) < Tnow) {
-                            c_proc++;
-                            if (is_dense(oi[q])) { dn[q] = true; continue; }
-                            const float h = (ca[q] - vp[q]) - ord2f(dord);
-                            if (lane < KCU && col[q] != COLSENT && (int)col[q] != pj[q]) {
-                                const unsigned long long lv = edge_lv(f2ord((val[q] - ld_sc1(a.v + col[q])) - h), dord, kq);
-                                if (lv <= Tnow) { off[q] = true; co[q] = lv; old[q] = offer((int)col[q], lv, oi[q]); }
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int q = 0; q < AP; q++) {
-                        const bool better = off[q] && (lkey(co[q], (uint32_t)oi[q]) < old[q]);
-                        if (__ballot(better) && better) after_offer((int)col[q], co[q], oi[q], old[q]);
-                    }
-#pragma unroll
-                    for (int q = 0; q < AP; q++) {
-                        if (!dn[q]) continue;                      // the owner's cache could not certify: its whole cost row
-                        const uint32_t dord = (uint32_t)(lab[q] >> 32), kq = (uint32_t)(lab[q] >> 20) & LKMAX;
-                        const float h = (ca[q] - vp[q]) - ord2f(dord);
-                        const float *__restrict__ row = a.cost + wrow_off(a.rowmap, oi[q], a.ld);
-                        const int pjq = pj[q], oiq = oi[q];
-                        const unsigned long long Tsw = uni(lv_of(ld_sc1(&c->T)));        // (once per sweep: a stale bound only prunes less)
-                        wave_row_sweep(row, n, lane, [&](int cidx, float x) {
-                            const unsigned long long lv = edge_lv(f2ord((x - ld_sc1(a.v + cidx)) - h), dord, kq);
-                            if (cidx != pjq && lv <= Tsw && (lkey(lv, (uint32_t)oiq) < ld_sc1(a.label + cidx))) relax_to(cidx, lv, oiq);
-                        });
-                        c_dense++;
-                    }
-                    // the blocks this wave took from: their smallest dirty column now
-#pragma unroll
-                    for (int q = 0; q < AP; q++)
-                        if (pk[q] && lane == 0) st_sc1(a.gbmin + (int64_t)(pj[q] >> 6) * MC_REC, ~0ull);
-                    MC_WAIT_VM();                                   // (also: this wave's own dirty bits and block-minimum updates are in place)
-#pragma unroll
-                    for (int q = 0; q < AP; q++) {
-                        if (!pk[q]) continue;
-                        const int b = pj[q] >> 6, cc = b * 64 + lane;
-                        const bool db = cc < n && ((uni(ld_sc1(a.gbmin + (int64_t)b * MC_REC + 1)) >> lane) & 1ull);
-                        if (__ballot(db)) {
-                            const unsigned long long lb = db ? ld_sc1(a.label + cc) : ~0ull;
-                            const uint32_t dk = (uint32_t)(lb >> 32);
-                            const uint32_t m = wave_min_u32(dk);
-                            const uint32_t lo2 = (db && dk == m) ? (((uint32_t)lb & 0xFFF00000u) | (uint32_t)cc) : 0xFFFFFFFFu;
-                            const uint32_t m2 = wave_min_u32(lo2);
-                            if (lane == 0) atomicMin(a.gbmin + (int64_t)b * MC_REC, ((unsigned long long)m << 32) | m2);
-                        }
-                    }
-                }
-                c_macro++;
-                mc_barrier(c, G, gen);
-                const int prog = uni(ld_sc1(&c->progress[par]));
-                if (gtid == 0) { st_sc1(&c->progress[par ^ 1], 0); st_sc1(&c->active, W); }
-                par ^= 1;
-                mc_barrier(c, G, gen);
-                if (!prog || ld_sc1(&c->err)) break;
-            }
-            // ================= converged: do the caches certify what was skipped? =================
-            const unsigned long long Tk = ld_sc1(&c->T);
-            const uint32_t Dord = (uint32_t)(Tk >> 32);
-            const float D = Tk == ~0ull ? INFINITY : ord2f(Dord);
-            const int nt = uni(ld_sc1(&c->ntouch));
-            for (int q = gtid; q < nt; q += GT) {
-                const int k = ld_sc1(a.touched + q);
-                const unsigned long long lbk = ld_sc1(a.label + k);
-                const uint32_t dord = (uint32_t)(lbk >> 32);
-                if (lv_of(lbk) < lv_of(Tk) && is_asg(k)) {             // (every settled column: see wide_aug)
-                    const int i = ld_sc1(a.colsol + k);
-                    if (!is_dense(i)) {
-                        const float h = (ld_sc1(a.cassign + k) - ld_sc1(a.v + k)) - ord2f(dord);
-                        const float bound = a.cache_val[(int64_t)i * KC + KCU] - h;
-                        if (!(bound > D)) {
-                            atomicOr(a.gdense + (i >> 5), 1u << (i & 31));
-                            atomicOr(a.gbmin + (int64_t)(k >> 6) * MC_REC + 1, 1ull << (k & 63));
-                            MC_WAIT_VM();
-                            atomicMin(a.gbmin + (int64_t)(k >> 6) * MC_REC, lkey(lv_of(lbk), (uint32_t)k));
-                            atomicAdd(&c->fail, 1);
-                        }
-                    }
-                }
-            }
-            if (gtid == 0 && !ld_sc1(&c->rootdense) && !(ftau > D)) { st_sc1(&c->rootdense, 1); st_sc1(&c->doroot, 1); atomicAdd(&c->fail, 1); }
-            c_verify++;
-            mc_barrier(c, G, gen);
-            const int fail = uni(ld_sc1(&c->fail)), doroot = uni(ld_sc1(&c->doroot));
-            if (doroot)
-                for (int cc = gtid; cc < n; cc += GT) {
-                    const unsigned long long lv = (unsigned long long)f2ord(frow[cc] - ld_sc1(a.v + cc)) << 12;
-                    if (lv <= lv_of(ld_sc1(&c->T)) && (lkey(lv, (uint32_t)fr) < ld_sc1(a.label + cc))) relax_to(cc, lv, fr);
-                }
-            mc_barrier(c, G, gen);
-            if (gtid == 0) { if (fail) st_sc1(&c->anydense, 1); st_sc1(&c->fail, 0); st_sc1(&c->doroot, 0); }
-            if (!fail || ld_sc1(&c->err)) break;
-            mc_barrier(c, G, gen);                                  // (the resets above are in place before anyone counts failures again)
-        }
-
-        // ---- the search has ended at T: price update, path flip, reset ----
-        const unsigned long long Tk = ld_sc1(&c->T);
-        if (Tk == ~0ull || ld_sc1(&c->err)) { if (gtid == 0 && Tk == ~0ull) atomicExch(&c->err, 1); break; }
-        const uint32_t Dord = (uint32_t)(Tk >> 32);
-        const float D = ord2f(Dord);
-        const int sink = (int)lid_of(Tk);
-        const int nt = uni(ld_sc1(&c->ntouch));
-        const int anydense = uni(ld_sc1(&c->anydense));
-        int myscans = 0;
-        for (int q = gtid; q < nt; q += GT) {
-            const int k = ld_sc1(a.touched + q);
-            const uint32_t dord = (uint32_t)(ld_sc1(a.label + k) >> 32);
-            if (dord < Dord && is_asg(k)) {
-                const float vk = ld_sc1(a.v + k);
-                const float nv = (vk + ord2f(dord)) - D;
-                if (nv < vk) st_sc1(a.v + k, nv);
-                myscans++;
-            }
-        }
-        if (myscans) atomicAdd(&c->scans, myscans);
-        if (gtid == 0) {
-            int j = sink;
-            for (;;) {
-                const int i = (int)lid_of(ld_sc1(a.label + j));
-                const int jn = ld_sc1(a.rowsol + i);
-                st_sc1(a.colsol + j, (int32_t)i); st_sc1(a.rowsol + i, (int32_t)j); st_sc1(a.cassign + j, a.cost[wrow_off(a.rowmap, i, a.ld) + j]);
-                c_hops++;
-                if (i == fr) break;
-                j = jn;
-            }
-            atomicOr(a.gasg + (sink >> 5), 1u << (sink & 31));
-        }
-        mc_barrier(c, G, gen);
-        for (int q = gtid; q < nt; q += GT) {
-            const int k = ld_sc1(a.touched + q);
-            st_sc1(a.label + k, ~0ull);
-            atomicAnd(a.gbmin + (int64_t)(k >> 6) * MC_REC + 1, ~(1ull << (k & 63)));
-            st_sc1(a.gbmin + (int64_t)(k >> 6) * MC_REC, ~0ull);
-        }
-        if (anydense) for (int q = gtid; q < nw32; q += GT) st_sc1(a.gdense + q, 0u);
-        if (gtid == 0) {
-            c->c_relax += ld_sc1(&c->scans);
-            st_sc1(&c->scans, 0); st_sc1(&c->T, ~0ull); st_sc1(&c->ntouch, 0); st_sc1(&c->anydense, 0); st_sc1(&c->rootdense, 0); st_sc1(&c->f, f + 1);
-        }
-        f++;
-        mc_barrier(c, G, gen);
-    }
-
-    // ---- counters of every wave; duals and total by workgroup 0 ----
-    if (lane == 0) {
-        atomicAdd(reinterpret_cast<unsigned long long *>(&c->c_proc), (unsigned long long)c_proc);
-        atomicAdd(reinterpret_cast<unsigned long long *>(&c->c_dense), (unsigned long long)c_dense);
-        if (g == 0 && w == 0) { c->c_trivial = c_trivial; c->c_hops += c_hops; c->c_macro = c_macro; c->c_verify = c_verify; }
-    }
-    mc_barrier(c, G, gen);
-    if (g != 0) return;
-    double tot = 0.0;
-    for (int i = tid; i < n; i += WT) {
-        const int j = ld_sc1(a.rowsol + i);
-        if (j >= 0) {
-            const float cij = ld_sc1(a.cassign + j);
-            a.u[i] = cij - ld_sc1(a.v + j);
-            tot += (double)cij;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off);
-    if (lane == 0) s_tot[w] = tot;
-    __syncthreads();
-    if (tid == 0) {
-        double t = 0.0;
-        for (int k = 0; k < WNW; k++) t += s_tot[k];
-        *reinterpret_cast<double *>(a.misc + 8) = t;
-        long long *ctr = reinterpret_cast<long long *>(a.misc + 16);
-        long long *wc = reinterpret_cast<long long *>(a.misc + 160);
-        ctr[C_AUG_INIT] = numfree; ctr[C_AUG_RELAX] = c->c_relax; ctr[C_AUGS] = numfree; ctr[C_HOPS] = c->c_hops;
-        wc[WC_DENSE_AUG] = ld_sc1(&c->c_dense); wc[WC_AUG_ROUNDS] = c->c_macro; wc[WC_AUG_PROCESSED] = ld_sc1(&c->c_proc);
-        wc[WC_TRIVIAL] = c->c_trivial; wc[WC_VERIFY_PASSES] = c->c_verify;
-        if (ld_sc1(&c->err)) *reinterpret_cast<int *>(a.misc + 4) = 1;
     }
 }
 
@@ -2571,13 +2215,13 @@ struct SpinWait {
     }
 };
 
-size_t wide_sc_ones_bytes(int n) { return (((size_t)n + 63) & ~(size_t)63) * (2 * 8); }
-size_t wide_sc_ext_bytes(int n) {
+static size_t wide_sc_ones_bytes(int n) { return (((size_t)n + 63) & ~(size_t)63) * (2 * 8); }
+static size_t wide_sc_ext_bytes(int n) {
     const size_t np = ((size_t)n + 63) & ~(size_t)63;
     return np * (2 * 8 + 2 * 4 + 2 * 16 + 2 * 4);
 }
 
-int wide_launch_claims(const WideArgs *d_args, int nb, int n, hipStream_t stream, int32_t *d_sync) {
+static int wide_launch_claims(const WideArgs *d_args, int nb, int n, hipStream_t stream, int32_t *d_sync) {
     // the one-edge searches of every problem, on the whole chip (above); rounds in groups of four, then "did anything move?" -- reported
     // into pinned host memory: the driver keeps two groups queued ahead of the one under way and never waits for the stream
     if (n < 2 || !d_sync) return CYTO_OK;
@@ -2623,15 +2267,15 @@ int wide_launch_claims(const WideArgs *d_args, int nb, int n, hipStream_t stream
     return CYTO_OK;                                                       // (the pinned block: usable again behind the check kernels still queued)
 }
 
-int wide_launch_rt(const WideArgs *d_args, int nb, int n, hipStream_t stream) {
+static int wide_launch_rt(const WideArgs *d_args, int nb, int n, hipStream_t stream) {
     const int blocks = std::max(1, std::min((n + RTB / 64 - 1) / (RTB / 64), 2048 / std::max(1, std::min(nb, 8))));
     hipLaunchKernelGGL(wide_rt, dim3(blocks, nb), dim3(RTB), 0, stream, d_args);
     CYTO_HIP(hipGetLastError());
     return CYTO_OK;
 }
 
-int wide_launch_arr(const WideArgs *d_args, int nb, int n, hipStream_t stream, int wipe_every, bool resume, int32_t *d_sync,
-                    int (*rebuild)(void *ctx, const int32_t *flags), void *ctx, const WideArgs *direct) {
+static int wide_launch_arr(const WideArgs *d_args, int nb, int n, hipStream_t stream, int wipe_every, bool resume, int32_t *d_sync,
+                           int (*rebuild)(void *ctx, const int32_t *flags), void *ctx, const WideArgs *direct) {
     // The phase machine on the whole chip (one launch per round), in groups of launches: after a group the driver asks which problems
     // are not through (one small read) and rebuilds the row caches of those whose floors have gone stale; then wide_arr -- one
     // workgroup per problem -- for the chain rounds of the problems that did not scale (<= 64 active rows) and the free lists.
@@ -2712,12 +2356,7 @@ int wide_launch_arr(const WideArgs *d_args, int nb, int n, hipStream_t stream, i
     return CYTO_OK;
 }
 
-int wide_launch_aug(const WideArgs *d_args, int nb, int n, hipStream_t stream, int mc_groups, int par_groups) {
-    if (mc_groups > 0) {                                           // one problem, several workgroups (blocks 0, 8, 16 ... take part)
-        hipLaunchKernelGGL(wide_aug_mc, dim3(8 * mc_groups), dim3(WT), 0, stream, d_args);
-        CYTO_HIP(hipGetLastError());
-        return CYTO_OK;
-    }
+static int wide_launch_aug(const WideArgs *d_args, int nb, int n, hipStream_t stream, int par_groups) {
     const bool vlds = wide_aug_vlds(n), clds = wide_aug_clds(n);
     const size_t shm = wide_aug_lds_bytes(n, vlds, clds);
     if (shm > (size_t)LDS_DYNAMIC_MAX) return CYTO_ERR_UNSUPPORTED;
@@ -2737,6 +2376,144 @@ int wide_launch_aug(const WideArgs *d_args, int nb, int n, hipStream_t stream, i
     if (rc) return rc;
     hipLaunchKernelGGL(k, dim3(nb), dim3(WT), shm, stream, d_args);
     CYTO_HIP(hipGetLastError());
+    return CYTO_OK;
+}
+
+static std::atomic<int> g_par_busy[64];     // per device: a several-searches-at-once kernel (wide_aug<..,PAR>) is in flight
+
+int wide_solve_batch(const WidePlan &pl, const std::vector<WideJob> &jobs, hipStream_t stream, hipEvent_t ev_cache_done,
+                     hipEvent_t ev_arr_done) {
+    const int n = pl.n, nl = (int)jobs.size();
+    if (!nl) return CYTO_OK;
+    int rc;
+    auto build_caches_of = [&](const int32_t *flags) -> int {    // flags: per problem, 0 = nothing left to do for it (or null: all)
+        for (int k = 0; k < nl; k++) {
+            if (flags && flags[k] == 0) continue;
+            const WideJob &j = jobs[(size_t)k];
+            const int r = build_caches(pl.cache, n, j.ld, j.cost, j.rowmap, j.fws, j.cache_col, j.cache_val, j.same, stream);
+            if (r) return r;
+        }
+        return CYTO_OK;
+    };
+    if ((rc = build_caches_of(nullptr))) return rc;
+    CYTO_HIP(hipEventRecord(ev_cache_done, stream));
+    struct ParSlot { std::atomic<int> *p = nullptr; ~ParSlot() { if (p) p->store(0); } } par_slot;       // (released on every return path)
+    int dev_now = 0;
+    (void)hipGetDevice(&dev_now);
+    const int device_slot = dev_now >= 0 && dev_now < 64 ? dev_now : 0;
+    const size_t nT = (size_t)n * sizeof(float);
+    std::vector<WideArgs> h_wa((size_t)nl);
+    for (int k = 0; k < nl; k++) {
+        const WideJob &j = jobs[(size_t)k];
+        // Several searches of ONE problem at once (wide_aug<.., PAR>): by default for a single problem without runs of identical rows
+        // from 2 048 rows on (runs of identical rows -- a Visium problem's slots: a tenth as many groups as rows -- finish most of their
+        // searches as runs of one-edge steps in the one-workgroup kernel; a sub-spot chunk's few doubled spots do not matter).
+        // Its workgroups meet at hand-rolled grid barriers and it is launched as a plain kernel: they must all be RESIDENT, one
+        // 1024-thread workgroup per CU.  So G is clamped to the CUs of one XCD, and ONE such kernel runs per device at a time: workgroups
+        // of two of them could each get partly scheduled and spin for the rest.  A solve that finds the slot taken runs one search at a
+        // time on one workgroup (same results).
+        const int xcd_cus = std::max(1, pl.cache.cus / 8);
+        const bool dup_rows = n >= 2 && (long long)j.ngroups * 5 < (long long)n * 4;
+        int parg = nl != 1 ? 0 : (pl.par > 0 ? pl.par : (pl.par < 0 || dup_rows || n < 2048 ? 0 : 16));
+        parg = std::min(std::min(parg, WIDE_PAR_GMAX), xcd_cus);
+        if (parg == 1) parg = 0;
+        if (parg > 1) {
+            if (g_par_busy[device_slot].exchange(1) != 0) parg = 0;
+            else par_slot.p = &g_par_busy[device_slot];
+        }
+        const size_t parb = parg > 0 ? wide_par_state_bytes(n, parg) : 0;
+        const size_t sc_off = ((2 * nT + 255) / 256) * 256;            // the phase machine's control block behind everything else
+        const size_t par_off = sc_off + WIDE_SC_BYTES;
+        const size_t scx_off = ((par_off + parb + 255) / 256) * 256;     // the machine's own arrays (ScMem)
+        if ((rc = j.state->alloc(scx_off + wide_sc_ext_bytes(n), stream))) return rc;
+        WideArgs &wa = h_wa[(size_t)k];
+        wa.n = n; wa.ld = j.ld; wa.cost = j.cost; wa.rowmap = j.rowmap;
+        wa.v = j.fws; wa.u = j.fws + n; wa.cassign = j.fws + 3 * (int64_t)n;
+        wa.label = reinterpret_cast<unsigned long long *>(j.fws + 4 * (int64_t)n);
+        wa.rowsol = j.iws; wa.colsol = j.iws + n; wa.matches = j.iws + 2 * (int64_t)n; wa.freerows = j.iws + 3 * (int64_t)n;
+        wa.act0 = j.iws + 4 * (int64_t)n; wa.act1 = j.iws + 5 * (int64_t)n; wa.touched = j.iws + 6 * (int64_t)n;
+        wa.slot_j = j.iws + 7 * (int64_t)n;
+        wa.bid = reinterpret_cast<unsigned long long *>(j.iws + 8 * (int64_t)n);
+        wa.slot_p = j.state->as<float>(); wa.slot_c = wa.slot_p + n;
+        wa.cache_col = j.cache_col; wa.cache_val = j.cache_val; wa.misc = j.misc;
+        wa.max_rounds = pl.rounds;
+        wa.aug_seg = pl.rebuild;
+        // what a rebuild costs, in full-row relaxations of ONE workgroup (a relaxation sweeps n elements at ~5 G/s; a pass costs
+        // ~0.4 ms of launches and synchronisation plus one read of every unfinished problem's matrix by the whole chip, ~100x
+        // faster per element -- and the problems of a batch are rebuilt one after the other while their workgroups all wait)
+        wa.aug_waste = (int)std::min<long long>(1 << 30, std::max<long long>(16, (2000000ll + (long long)nl * n * n / 100) / n));
+        wa.arr_waste = std::max(8, wa.aug_waste / 3);          // (a full-row bid with its cache refresh: three sweeps)
+        if (CYTO_KNOB("CYTO_ARR_WASTE").set) wa.arr_waste = std::max(1, CYTO_KNOB("CYTO_ARR_WASTE").value);     // (developer knob, read once per process: tools/batch_chunks_bench.py)
+        wa.seg_quorum = nl > 1 ? std::max(1, nl / 4) : 0;
+        wa.seg_sync = nullptr;
+        wa.same_prev = j.same;
+        wa.sc = j.state->as<char>() + sc_off;
+        CYTO_HIP(hipMemsetAsync(wa.sc, 0, WIDE_SC_BYTES, stream));
+        wa.scx = j.state->as<char>() + scx_off;
+        CYTO_HIP(hipMemsetAsync(wa.scx, 0, wide_sc_ext_bytes(n), stream));
+        CYTO_HIP(hipMemsetAsync(wa.scx, 0xFF, wide_sc_ones_bytes(n), stream));     // (the machine's bid words and lowest-bid arrays)
+        wa.par_groups = parg; wa.par = nullptr;
+        if (parg > 0) {
+            const size_t np_ = ((size_t)n + 63) & ~(size_t)63;
+            wa.par = j.state->as<char>() + par_off;
+            CYTO_HIP(hipMemsetAsync(wa.par, 0, 256, stream));                                            // the control block ...
+            const int p_init[2] = {WIDE_PAR_GMAX + 1, WIDE_PAR_GMAX + 1};
+            CYTO_HIP(hipMemcpyAsync(wa.par + 8, p_init, sizeof p_init, hipMemcpyHostToDevice, stream));   // ... P[0], P[1]: "no conflict"
+            CYTO_HIP(hipMemsetAsync(wa.par + 256, 0xFF, (size_t)parg * np_ * 8, stream));                  // every search's labels: all-ones
+            CYTO_HIP(hipMemsetAsync(wa.par + 256 + (size_t)parg * np_ * 20, 0, np_ * 4, stream));          // the claim words
+            CYTO_HIP(hipStreamSynchronize(stream));                                                         // (p_init is a local)
+        }
+        // the post-column-reduction prices: snapshot for the reduction transfer AND the raw cost of every owner entry
+        CYTO_HIP(hipMemcpyAsync(wa.cassign, wa.v, nT, hipMemcpyDeviceToDevice, stream));
+        CYTO_HIP(hipMemsetAsync(wa.label, 0xFF, 2 * nT, stream));
+        CYTO_HIP(hipMemsetAsync(wa.bid, 0xFF, 2 * nT, stream));
+    }
+    DevBuf d_wa, d_sync;
+    if ((rc = d_wa.alloc(sizeof(WideArgs) * nl, stream)) || (rc = d_sync.alloc(sizeof(int32_t) * ((size_t)nl + 1), stream))) return rc;
+    for (WideArgs &wa : h_wa) wa.seg_sync = d_sync.as<int32_t>();
+    CYTO_HIP(hipMemcpyAsync(d_wa.p, h_wa.data(), sizeof(WideArgs) * nl, hipMemcpyHostToDevice, stream));
+    if ((rc = wide_launch_rt(d_wa.as<WideArgs>(), nl, n, stream))) return rc;
+    std::vector<int32_t> h_sync((size_t)nl + 1, 1);
+    std::vector<int32_t> caches_fresh((size_t)nl, 0);           // (wide_arr's word: hardly a full-row bid -- no rebuild before the searches)
+    using BuildFn = decltype(build_caches_of);
+    auto rebuild_tramp = +[](void *ctx, const int32_t *flags) -> int { return (*static_cast<BuildFn *>(ctx))(flags); };
+    for (int pass = 0;; pass++) {                              // the row-reduction rounds (they pause when the caches have gone stale)
+        if (pass && (rc = build_caches_of(h_sync.data() + 1))) return rc;
+        CYTO_HIP(hipMemsetAsync(d_sync.p, 0, sizeof(int32_t), stream));
+        if ((rc = wide_launch_arr(d_wa.as<WideArgs>(), nl, n, stream, pl.wipe, pass > 0, d_sync.as<int32_t>(), rebuild_tramp, &build_caches_of,
+                                  nl == 1 ? &h_wa[0] : nullptr))) return rc;
+        if (h_wa[0].aug_seg != 0) break;                       // (no pauses asked for: nothing to wait for)
+        CYTO_HIP(hipMemcpyAsync(h_sync.data(), d_sync.p, sizeof(int32_t) * ((size_t)nl + 1), hipMemcpyDeviceToHost, stream));
+        CYTO_HIP(hipStreamSynchronize(stream));
+        bool done = true;
+        for (int k = 0; k < nl; k++) { done = done && (h_sync[(size_t)k + 1] & 1) == 0; caches_fresh[(size_t)k] = (h_sync[(size_t)k + 1] & 2) != 0; h_sync[(size_t)k + 1] &= 1; }
+        if (done) break;
+    }
+    // the searches, in as many launches as they ask for: wide_aug returns when its row caches have gone stale and the whole chip
+    // rebuilds them against the prices reached -- only for the problems that still have searches to run
+    const int parg = h_wa[0].par_groups;
+    for (int pass = 0;; pass++) {
+        if (pass == 0) {
+            std::vector<int32_t> need((size_t)nl);
+            for (int k = 0; k < nl; k++) need[(size_t)k] = caches_fresh[(size_t)k] ? 0 : 1;
+            if ((rc = build_caches_of(need.data()))) return rc;
+        } else if ((rc = build_caches_of(h_sync.data() + 1))) return rc;
+        if (pass == 0) CYTO_HIP(hipEventRecord(ev_arr_done, stream));   // (ms_aug: the search kernel -- and what later passes add)
+        if (pass == 0 && parg == 0) {
+            // repeated spot rows (CytoSPACE's slots): their one-edge searches all at once, before the search kernel
+            bool dup = false;
+            for (int k = 0; k < nl; k++) dup = dup || h_wa[(size_t)k].same_prev != nullptr;
+            if (dup && (rc = wide_launch_claims(d_wa.as<WideArgs>(), nl, n, stream, d_sync.as<int32_t>()))) return rc;
+        }
+        CYTO_HIP(hipMemsetAsync(d_sync.p, 0, sizeof(int32_t), stream));
+        if ((rc = wide_launch_aug(d_wa.as<WideArgs>(), nl, n, stream, parg))) return rc;
+        if (parg > 0) { CYTO_HIP(hipStreamSynchronize(stream)); break; }
+        CYTO_HIP(hipMemcpyAsync(h_sync.data(), d_sync.p, sizeof(int32_t) * ((size_t)nl + 1), hipMemcpyDeviceToHost, stream));
+        CYTO_HIP(hipStreamSynchronize(stream));                // (d_wa is read by the kernels until here)
+        bool done = true;
+        for (int k = 0; k < nl; k++) done = done && h_sync[(size_t)k + 1] == 0;
+        if (done) break;
+    }
     return CYTO_OK;
 }
 

@@ -152,9 +152,8 @@ typedef struct {
                                    shortest paths with (distance, tight-hop) labels -- same file, "WIDE MODE"; float32).  Both reach the same optimum;
                                    the duals and, where the optimum is not unique, the particular optimal assignment differ */
     int32_t wide_rounds;        /* wide solver: budget of row-reduction rounds.  0: 4096 + n / 4.  -1: none */
-    int32_t wide_groups;        /* wide solver, one problem: workgroups that run a search together, asynchronously, with the search
-                                   state in L2 (wide_aug_mc).  0 / -1: one workgroup, state in LDS (faster on everything but
-                                   few-cell-type chunks).  k > 0: k (<= 32).  Results do not depend on it */
+    int32_t wide_groups;        /* retired (it selected a search on several workgroups, since removed): accepted in -1 ... 32 and
+                                   ignored.  Results never depended on it */
     int32_t wide_rebuild;       /* wide solver, augmentation: when the searches pause for the row caches to be rebuilt by the whole chip against
                                    the prices reached (a floor goes stale as searches lower the prices; deep-search instances otherwise
                                    fall back to full cost rows).  0: when the full-row relaxations since the last rebuild have cost what
@@ -167,8 +166,8 @@ typedef struct {
     int32_t wide_wipe;          /* wide solver, row reduction: the per-column bid words carry a 12-bit round tag relative to their last wipe;
                                    0: each of the two word buffers is wiped every 1 024 of its launches.  k > 0: every k (a self-test of the protocol at sizes the CPU
                                    oracle checks).  Results do not depend on it */
-    int32_t cache_waves;        /* row-cache builder (float32): 0: by size (a wave per row, 8 or 20 waves per CU).  k > 0: k waves per CU (<= 32).
-                                   -1: the workgroup-per-row builders of round 3.  Results do not depend on it */
+    int32_t cache_waves;        /* row-cache builder (float32): 0 / -1: by size (a wave per row, 8 or 20 waves per CU).  k > 0: k waves per CU
+                                   (<= 32).  (-1 selected the workgroup-per-row builders of round 3, since removed.)  Results do not depend on it */
     int32_t cache_unroll;       /* ... 16-byte quads in flight per lane of the wave builder: 0 (default: 8), 4 or 8 */
     int32_t cache_stream;       /* ... 0 / 1: the guess-free streaming selection for rows of >= 2 048 columns.  -1: a neighbouring row's floor
                                    as the guess (round 4's first form) */

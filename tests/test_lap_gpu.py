@@ -403,7 +403,7 @@ def test_duplicate_row_group_state_in_global_memory(aug):
 
 
 def test_chain_solver_tie_between_two_groups_of_one_lane():
-    # Regression (tools/stress_lap.py seed 2407: n = 4 750, rows in runs of identical copies; found by tools/trace_aug_scans.py).  In
+    # Regression (tools/stress_lap.py seed 2407: n = 4 750, rows in runs of identical copies; found by a scan-trace build, since removed).  In
     # search 92 an assigned and an UNASSIGNED column sit at the same (final) distance in two different groups of four of the SAME lane
     # of the dense augmentation kernel: the pick's one-holder shortcut looked at the first such group only and scanned the assigned
     # column before ending at the unassigned one -- 126 544 scans against the oracle's 126 543, everything else identical (a scan AT
@@ -587,37 +587,41 @@ def test_wide_uniform_larger(n):
     assert g["info"].wide_aug_settled >= g["info"].scans_aug_relax        # speculative: a column may be settled more than once
 
 
-@pytest.mark.parametrize("groups", [2, 5, 16])
-def test_wide_search_on_several_workgroups(groups):
-    # cyto_lap_opts.wide_groups: the augmentation's searches run on several workgroups at once, asynchronously (no barrier inside a
-    # search's steady state; labels, dirty bits and block minima exchanged through agent-scope atomics in L2).  The labels are the
-    # fixed point of a monotone system, so who settles what when cannot matter: the oracle's answer bit for bit, every time.
-    rng = np.random.default_rng(40 + groups)
-    cases = [rng.random((n, n)).astype(np.float32) for n in (3, 64, 700, 2300)]
-    cases.append(np.repeat(rng.random((150, 600)), 4, axis=0).astype(np.float32))                     # duplicated rows: tight cycles
-    cases.append(rng.integers(0, 10, (400, 400)).astype(np.float32))                                    # heavy ties
-    prof = rng.normal(size=(6, 64)).astype(np.float32)                                                  # few cell types: full-row relaxations
-    rows = prof[rng.integers(0, 6, 1200)] + 0.05 * rng.normal(size=(1200, 64)).astype(np.float32)
-    cols = prof[rng.integers(0, 6, 1200)] + 0.05 * rng.normal(size=(1200, 64)).astype(np.float32)
-    cases.append(-(rows @ cols.T).astype(np.float32))
-    for c in cases:
-        for rounds in (0, 2):                                    # (a short row reduction leaves many searches)
-            g, o = _check_wide(c, opts=dict(wide_groups=groups), rounds=rounds)
-            assert g["info"].wide == 1
+def test_wide_search_corner_cases():
+    # the searches on the shapes that stress them -- tiny and ragged sizes, duplicated rows (tight cycles), heavy ties, few cell types
+    # (full-row relaxations) -- after a full and a short row reduction (many searches left): the oracle's answer bit for bit.
+    # (These instances came with the several-workgroups search, cyto_lap_opts.wide_groups, which is retired: the option is accepted
+    #  and ignored.)
+    for seed in (42, 45, 56):
+        rng = np.random.default_rng(seed)
+        cases = [rng.random((n, n)).astype(np.float32) for n in (3, 64, 700, 2300)]
+        cases.append(np.repeat(rng.random((150, 600)), 4, axis=0).astype(np.float32))                 # duplicated rows: tight cycles
+        cases.append(rng.integers(0, 10, (400, 400)).astype(np.float32))                                # heavy ties
+        prof = rng.normal(size=(6, 64)).astype(np.float32)                                              # few cell types: full-row relaxations
+        rows = prof[rng.integers(0, 6, 1200)] + 0.05 * rng.normal(size=(1200, 64)).astype(np.float32)
+        cols = prof[rng.integers(0, 6, 1200)] + 0.05 * rng.normal(size=(1200, 64)).astype(np.float32)
+        cases.append(-(rows @ cols.T).astype(np.float32))
+        for c in cases:
+            for rounds in (0, 2):                                # (a short row reduction leaves many searches)
+                g, o = _check_wide(c, rounds=rounds)
+                assert g["info"].wide == 1
+    g4 = lap_solve(c, np.float32, return_info=True, opts=dict(WIDE, wide_rounds=2, wide_groups=4))
+    for k in ("rowsol", "colsol", "u", "v", "total"):
+        assert np.array_equal(g4[k], g[k]), k
 
 
-@pytest.mark.parametrize("waves", ["0", "1", "8", "32", "8-guess"])
+@pytest.mark.parametrize("waves", ["1", "8", "32", "8-guess"])
 def test_row_cache_builders_agree(waves):
     # The full-chip cache build: build_row_caches_wave (a wave per row, guessed floor, one sweep; cyto_lap_opts.cache_waves waves per CU --
-    # with 1 a wave takes many rows and its guesses matter, with 32 most rows are a wave's first and take the lane-minima floor) or, with
-    # "0" (cache_waves = -1), the workgroup-per-row builders of rounds 1-3.  Which columns a cache holds is a matter of speed only: both
-    # solvers give the oracle's answers bit for bit with every builder -- on uniform, few-cell-type, tie-heavy (the floor search cannot
-    # separate: caches without entries) and duplicated-row instances, ragged sizes (n % 4 != 0, n < 64) included.
+    # with 1 a wave takes many rows and its guesses matter, with 32 most rows are a wave's first and take the lane-minima floor).  Which
+    # columns a cache holds is a matter of speed only: both solvers give the oracle's answers bit for bit with every setting -- on
+    # uniform, few-cell-type, tie-heavy (the floor search cannot separate: caches without entries) and duplicated-row instances,
+    # ragged sizes (n % 4 != 0, n < 64) included.
     # ("8-guess": cache_stream = -1, a neighbouring row's floor as the guess and the lane minima's 35th as the fallback, instead of the
     #  guess-free streaming selection of rows of >= 2 048 columns)
     stream = -1 if waves.endswith("guess") else 1
     waves = int(waves.split("-")[0])
-    bopts = dict(cache_waves=waves if waves > 0 else -1, cache_unroll=4 if waves == 1 else 8, cache_stream=stream)
+    bopts = dict(cache_waves=waves, cache_unroll=4 if waves == 1 else 8, cache_stream=stream)
     rng = np.random.default_rng(91)
     prof = rng.normal(size=(5, 48)).astype(np.float32)
     typed = -((prof[rng.integers(0, 5, 3001)] + 0.05 * rng.normal(size=(3001, 48)).astype(np.float32)) @
@@ -711,8 +715,7 @@ def test_wide_bid_words_wiped_every_few_rounds(wipe):
     _check_wide(np.repeat(rng.random((200, 1000)), 5, axis=0).astype(np.float32), opts=dict(wide_wipe=wipe))
 
 
-@pytest.mark.parametrize("groups", [0, 4])
-def test_wide_more_tight_hops_than_a_label_counts(groups):
+def test_wide_more_tight_hops_than_a_label_counts():
     # a band matrix: row i is cheap on columns i and i + 1 only.  The column reduction gives column j to row j - 1 and leaves row
     # n - 1 free and column 0 unassigned; with no row-reduction rounds the one search runs n - 1 TIGHT edges in a row (every
     # reduced cost on the path is exactly 0 past the root's) -- more than the 4095 a label's hop field counts: there the distance is
@@ -724,7 +727,7 @@ def test_wide_more_tight_hops_than_a_label_counts(groups):
     c[i, i] = 0.5
     c[i[:-1], i[:-1] + 1] = 0.5
     c[n - 1, n - 1] = 0.5 + 2.0 ** -10                     # the root's edge: a distance > 0 that the tight edges keep
-    g, o = _check_wide(c, opts=dict(wide_groups=groups), rounds=-1)
+    g, o = _check_wide(c, rounds=-1)
     assert o["stats"].path_hops == n and g["info"].path_hops == n           # one path through every row
     assert o["stats"].scans_aug_relax >= 4096
     u, v = g["u"].astype(np.float64), g["v"].astype(np.float64)
@@ -759,8 +762,7 @@ def test_wide_first_rounds_on_the_whole_chip(rounds):
     _check_wide(np.repeat(base, 10, axis=0), rounds=rounds)           # duplicated rows: most bids lose their round
 
 
-@pytest.mark.parametrize("groups", [0, 3])
-def test_wide_plateaus_every_distance_equal(groups):
+def test_wide_plateaus_every_distance_equal():
     # small integer costs: after the reductions every reduced cost in play is 0, so every label of a search has the SAME distance
     # and only the tight-hop counts order them (a breadth-first search in the tight subgraph).  Found by tools/stress_lap.py: the
     # certificate pass must cover every settled column -- also those at the end's distance with fewer hops --, an uncached tight
@@ -774,7 +776,7 @@ def test_wide_plateaus_every_distance_equal(groups):
             c = rng.integers(0, int(rng.integers(3, 50)), (n, n)).astype(np.float32)
         else:
             c = rng.integers(0, k, (n, n)).astype(np.float32)
-        _check_wide(c, opts=dict(wide_groups=groups))
+        _check_wide(c)
 
 
 def test_float64_certificate_of_a_float32_solve():

@@ -63,7 +63,7 @@ def _compare_with_golden(tag, buf, n, solve=None):
 def test_uniform_true_size(n):
     """c2 (20 000) and the north star's 50 000, and one size inside every chain variant's own range: <10,true> (20 000),
     <13,true> (24 000), <16,false> with u16 colsol in LDS and the prices in L2 (30 000), <0,false> with the streaming dense
-    refresh and build_row_caches_stream (33 000, 50 000)."""
+    refresh (33 000, 50 000)."""
     buf = instances.blocks_to_device(instances.uniform_cost_blocks(n), n)
     try:
         _compare_with_golden(f"u{n}", buf, n)

@@ -2,7 +2,7 @@
 # A variant build of the library for same-box A/B runs: tools/build_variant.sh <name> [extra hipcc flags for lap_wide.hip ...]
 #   -> cytospace_amd/build/libcytohip_<name>.so (git-ignored, travels to the GPU box); run with CYTOHIP_LIB=$GRAFT_REPO_ROOT/cytospace_amd/build/libcytohip_<name>.so
 # e.g.  tools/build_variant.sh coop0 -DCYTO_COOP_MIN_N=0      (tools/run/r06r.sh, r06z.sh)
-#       tools/build_variant.sh split -DCYTO_AUG_FIN_SPLIT     (tools/run/r06u.sh)
+#       tools/build_variant.sh stop128 -DWIDE_STOP_CAP=128
 # Only lap_wide.hip is recompiled (the other objects come from the last `python -m cytospace_amd.build`).
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)

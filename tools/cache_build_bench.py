@@ -1,6 +1,6 @@
 """Row-cache build kernels side by side (developer tool): `cyto_lap_info.ms_cache` (HIP events around the build that follows the
-column reduction) for the wave-per-row builder at several (waves per CU, quads in flight) settings and for the workgroup-per-row
-builders (cyto_lap_opts.cache_waves = -1), on a uniform n x n matrix resident in HBM.  The solve's results must not depend on the builder:
+column reduction) for the wave-per-row builder at several (waves per CU, quads in flight) settings, on a uniform n x n matrix
+resident in HBM.  The solve's results must not depend on the setting:
 rowsol/colsol/u/v and the counters of every setting are compared with the first one's.
 
     python tools/cache_build_bench.py 20000 50000 [--typed]
@@ -11,7 +11,7 @@ import numpy as np
 from cytospace_amd.lap import lap_solve
 from cytospace_amd import _lib
 
-SETTINGS = [("0", "4"), ("8", "4"), ("16", "4"), ("32", "4"), ("8", "8"), ("16", "8"), ("20", "8")]
+SETTINGS = [("8", "4"), ("16", "4"), ("32", "4"), ("8", "8"), ("16", "8"), ("20", "8")]
 
 
 def main():
@@ -26,7 +26,7 @@ def main():
         buf = _lib.DeviceBuffer.from_numpy(c)
         ref = None
         for waves, unroll in SETTINGS:
-            o = dict(cache_waves=int(waves) if int(waves) > 0 else -1, cache_unroll=int(unroll))
+            o = dict(cache_waves=int(waves), cache_unroll=int(unroll))
             best = 1e9
             for rep in range(4):
                 r = lap_solve(None, np.float32, return_info=True, device_ptr=buf.ptr, n=n, ld=n, opts=o)

@@ -1,7 +1,7 @@
 """Randomised parity stress against the CPU oracle (structures that reach the rare paths: duplicated rows, heavy integer ties,
 few cell types, constant columns, tiny and huge magnitudes).  Default: the float32 dispatch = the wide solver against the oracle's
-WIDE mode (--groups G: its searches on G workgroups; --rounds R: round budget; --rebuild K: row caches rebuilt every K searches, -1 never); --chain: the chain solver against the classic mode;
---f64: float64 through the streaming chain.  usage: stress_lap.py [seed0 count lo hi] [--chain | --f64] [--groups G] [--par K] [--wipe K] [--rounds R] [--rebuild K]"""
+WIDE mode (--rounds R: round budget; --rebuild K: row caches rebuilt every K searches, -1 never); --chain: the chain solver against the classic mode;
+--f64: float64 through the streaming chain.  usage: stress_lap.py [seed0 count lo hi] [--chain | --f64] [--par K] [--wipe K] [--rounds R] [--rebuild K]"""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -32,12 +32,12 @@ if __name__ == "__main__":
         if name in sys.argv:
             k = sys.argv.index(name); v = int(sys.argv[k + 1]); del sys.argv[k:k + 2]; return v
         return default
-    groups, rounds, rebuild, par, wipe = flag("--groups", 0), flag("--rounds", 0), flag("--rebuild", 0), flag("--par", 0), flag("--wipe", 0)
+    rounds, rebuild, par, wipe = flag("--rounds", 0), flag("--rebuild", 0), flag("--par", 0), flag("--wipe", 0)
     f64 = "--f64" in sys.argv                 # float64 through the streaming chain with row caches (chain_variant 1) at any size
     chain = "--chain" in sys.argv
     sys.argv = [a for a in sys.argv if a not in ("--f64", "--chain")]
     dt = np.float64 if f64 else np.float32
-    opts = dict(chain_variant=1) if f64 else (dict(mode=1) if chain else dict(mode=2, wide_groups=groups, wide_rounds=rounds, wide_rebuild=rebuild, wide_par=par, wide_wipe=wipe))
+    opts = dict(chain_variant=1) if f64 else (dict(mode=1) if chain else dict(mode=2, wide_rounds=rounds, wide_rebuild=rebuild, wide_par=par, wide_wipe=wipe))
     wide = not (f64 or chain)
     seed0 = int(sys.argv[1]) if len(sys.argv) > 1 else 0
     count = int(sys.argv[2]) if len(sys.argv) > 2 else 36

@@ -1,5 +1,5 @@
 """Wide solver at true sizes against the committed goldens (colsol; spot level where rows are duplicated) + timing.
-usage: wide_large.py [u20000 u50000 c3s50000 c4s10000 t20000 ...] [--chain] [--rounds R] [--groups G] [--par K | --par -1] [--rebuild K | --rebuild -1] [--reps K]"""
+usage: wide_large.py [u20000 u50000 c3s50000 c4s10000 t20000 ...] [--chain] [--rounds R] [--par K | --par -1] [--rebuild K | --rebuild -1] [--reps K]"""
 import os
 import sys
 import time
@@ -19,7 +19,6 @@ def main():
     mode = 1 if "--chain" in sys.argv else 2
     rounds = int(sys.argv[sys.argv.index("--rounds") + 1]) if "--rounds" in sys.argv else 0
     reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 2
-    groups = int(sys.argv[sys.argv.index("--groups") + 1]) if "--groups" in sys.argv else 0
     rebuild = int(sys.argv[sys.argv.index("--rebuild") + 1]) if "--rebuild" in sys.argv else 0
     par = int(sys.argv[sys.argv.index("--par") + 1]) if "--par" in sys.argv else 0
     for tag in tags:
@@ -40,7 +39,7 @@ def main():
             raise SystemExit(f"unknown tag {tag}")
         for rep in range(reps):
             t = time.time()
-            g = lap_solve(None, np.float32, return_info=True, device_ptr=buf.ptr, n=n, ld=n, opts=dict(mode=mode, wide_rounds=rounds, wide_groups=groups, wide_rebuild=rebuild, wide_par=par))
+            g = lap_solve(None, np.float32, return_info=True, device_ptr=buf.ptr, n=n, ld=n, opts=dict(mode=mode, wide_rounds=rounds, wide_rebuild=rebuild, wide_par=par))
             wall = time.time() - t
             inf = g["info"]
             same = np.array_equal(g["colsol"], d["colsol"])
