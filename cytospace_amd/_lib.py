@@ -38,7 +38,10 @@ class LapInfo(ctypes.Structure):
          ("wide_scaled", ctypes.c_int64), ("wide_phases", ctypes.c_int64), ("wide_par_batches", ctypes.c_int64),
          ("wide_par_discarded", ctypes.c_int64), ("f64_warm", ctypes.c_int64), ("f64_warm_ms", ctypes.c_double),
          ("certified", ctypes.c_int64), ("gap_f64", ctypes.c_double), ("gap_max_f64", ctypes.c_double), ("gap_rows", ctypes.c_int64),
-         ("polished", ctypes.c_int64), ("polish_ms", ctypes.c_double)]
+         ("polished", ctypes.c_int64), ("polish_ms", ctypes.c_double),
+         ("exact_status", ctypes.c_int64), ("exact_edges", ctypes.c_int64), ("exact_free_rows", ctypes.c_int64),
+         ("exact_changed_rows", ctypes.c_int64), ("exact_overflow_rows", ctypes.c_int64), ("exact_ms_emit", ctypes.c_double),
+         ("exact_ms_repair", ctypes.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
@@ -55,7 +58,7 @@ class LapOpts(ctypes.Structure):
                 ("inject_exceptions", ctypes.c_int32), ("group_state_global", ctypes.c_int32), ("aux_state_global", ctypes.c_int32), ("mode", ctypes.c_int32), ("wide_rounds", ctypes.c_int32), ("wide_groups", ctypes.c_int32), ("wide_rebuild", ctypes.c_int32),
                 ("wide_par", ctypes.c_int32), ("wide_wipe", ctypes.c_int32),
                 ("cache_waves", ctypes.c_int32), ("cache_unroll", ctypes.c_int32), ("cache_stream", ctypes.c_int32),
-                ("certify", ctypes.c_int32), ("polish", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+                ("certify", ctypes.c_int32), ("polish", ctypes.c_int32), ("exact", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
 
 
 class AssignInfo(ctypes.Structure):
@@ -143,6 +146,8 @@ def lib():
         L.cyto_lap_batch_f32.argtypes = [i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32]
         L.cyto_lap_batch_f32_opts.argtypes = [i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, ctypes.POINTER(LapOpts)]
         L.cyto_lap_batch_f32_opts.restype = ctypes.c_int
+        L.cyto_lap_repair_sparse.argtypes = [i32, vp, vp, vp, vp, vp]
+        L.cyto_lap_repair_sparse.restype = ctypes.c_int
         L.cyto_comm_unique_id.argtypes = [ctypes.c_char_p]
         L.cyto_comm_init.argtypes = [ctypes.c_char_p, i32, i32, i32, ctypes.POINTER(vp)]
         L.cyto_comm_init_local.argtypes = [i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(vp)]

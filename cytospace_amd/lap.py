@@ -53,7 +53,7 @@ def lap_solve(cost, dtype=np.float32, device_id=0, return_info=False, device_ptr
     cost        2-D square array-like (host) -- cast to `dtype` -- or None with `device_ptr`
     device_ptr  int address of a device-resident row-major matrix (then give n and ld)
     opts        None, or a dict of cyto_lap_opts fields (chain_variant, augmentation, no_handover, inject_exceptions):
-                kernel selection only, the results never depend on it
+                kernel selection only, the results never depend on it -- except certify / polish / exact (include/cytohip.h)
     Returns dict(rowsol, colsol, u, v, total[, info]).
     """
     L = _lib.lib()
@@ -106,14 +106,34 @@ def lap_solve(cost, dtype=np.float32, device_id=0, return_info=False, device_ptr
     return out
 
 
-def lapjv_hip(cost, verbose=0, force_doubles=False):
+def lapjv_hip(cost, verbose=0, force_doubles=False, exact=False):
     """Drop-in for `lapjv.lapjv`: returns (row_ind, col_ind, (total_cost, u, v)).
 
     Like lapjv 1.3.14 (recalled, unverified -- SURVEY.md section 8c) the solve runs in float32
-    unless force_doubles=True.
+    unless force_doubles=True.  exact=True (float32 only): the optimum of the float32 matrix, as
+    lapjv returns it -- the float32 solve repaired on its near-tight edges (cyto_lap_opts.exact).
     """
-    r = lap_solve(cost, dtype=np.float64 if force_doubles else np.float32)
+    if exact and force_doubles:
+        raise ValueError("exact applies to the float32 solve")
+    r = lap_solve(cost, dtype=np.float64 if force_doubles else np.float32, opts=dict(exact=1) if exact else None)
     return r["rowsol"], r["colsol"], (r["total"], r["u"], r["v"])
+
+
+def lap_repair_sparse(rowsol, row_ptr, cols, r):
+    """The host half of the exact option on its own (C ABI: cyto_lap_repair_sparse; no device): the optimum of the sparse
+    assignment problem whose row i has the edges cols[row_ptr[i]:row_ptr[i+1]] with float64 costs r (missing edges are infinite),
+    starting from the permutation rowsol, whose edges it must contain.  Returns the optimum's rowsol."""
+    L = _lib.lib()
+    rowsol = np.ascontiguousarray(rowsol, dtype=np.int32)
+    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
+    cols = np.ascontiguousarray(cols, dtype=np.int32)
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    n = len(rowsol)
+    if len(row_ptr) != n + 1 or len(cols) != len(r) or (n and row_ptr[-1] != len(cols)):
+        raise ValueError("row_ptr must have n + 1 entries ending at len(cols) == len(r)")
+    out = np.empty(n, np.int32)
+    _lib.check(L.cyto_lap_repair_sparse(n, rowsol.ctypes.data, row_ptr.ctypes.data, cols.ctypes.data, r.ctypes.data, out.ctypes.data))
+    return out
 
 
 def lap_solve_batch(costs, device_id=0, max_concurrent=0, return_info=False, opts=None):

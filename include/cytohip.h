@@ -120,6 +120,16 @@ typedef struct {
     int64_t polished;            /* cyto_lap_opts.polish: 1 = the certificate left a gap and the float64 polish ran (rowsol / colsol / total and
                                     the duals -- narrowed to float32 -- are the float64 solve's; gap_f64 is the float32 result's, before it) */
     double polish_ms;            /* kernel time of the polish */
+    /* float32, cyto_lap_opts.exact: the repair on the near-tight edges (gap_f64 / gap_max_f64 / gap_rows above still describe the float32
+       result before it) */
+    int64_t exact_status;        /* 0: not asked.  1: gap_f64 was 0, the result is already optimal.  2: repaired on E.  3: E went over its cap
+                                    (cyto_lap_opts.exact) and the float64 polish ran instead */
+    int64_t exact_edges;         /* edges of E besides the assignment's own: sum over rows of |{j != rowsol[i] : r_ij <= tau}| */
+    int64_t exact_free_rows;     /* rows the repair freed (r_ij < 0 for some j: == gap_rows) */
+    int64_t exact_changed_rows;  /* rows whose column the repair changed */
+    int64_t exact_overflow_rows; /* rows with more near-tight columns than the per-row slots (a second emission pass wrote them) */
+    double exact_ms_emit;        /* HIP-event time of the emission passes (near_tight_rows) */
+    double exact_ms_repair;      /* host wall time of building E and the sparse solve */
 } cyto_lap_info;
 
 int cyto_lap_f32(int n, const float *cost, int64_t ld, int cost_on_device,
@@ -180,7 +190,20 @@ typedef struct {
                                    every row free, the float64 augmenting row reduction and augmentation of the force_doubles path (~1.2 n steps):
                                    the optimum of the float32 matrix in float64 arithmetic, indices that do not depend on the float32 solver's
                                    constants.  Several times the cost of the solve: off by default.  (the second of the reserved words) */
-    int32_t reserved[3];        /* must be zero */
+    int32_t exact;              /* float32: the optimum of the float32 matrix (computed in float64), as lapjv returns it -- for single problems,
+                                   row maps and batches alike.  Implies certify.  With pi = the float32 result, v its prices, and in float64
+                                   w_ij = c_ij - v_j, r_ij = w_ij - w_i,pi(i) and gap = cyto_lap_info.gap_f64, every assignment at least as
+                                   good as pi lies in
+                                       E = { (i, j) : r_ij <= tau },   tau = gap * (1.0 + 0x1p-30)     (float64: one rounded multiply)
+                                   ("Exact option").  One more pass over the matrix emits E (the raw float32 costs), the rows
+                                   with r_ij < 0 are freed and a float64 successive-shortest-path solve over E on the host finishes.
+                                   v is returned unchanged; a changed row gets u_i = fl32(c_i,sigma(i) - v_sigma(i)).  gap == 0: nothing to
+                                   do.  0: off.  1: on, 16 edge slots per row.  k in 2 ... 64: k slots per row (a self-test of the
+                                   overflow pass).  Rows with more near-tight columns than slots are emitted again into an exact-size
+                                   list; when E holds more than max(2^22, 32 n) edges the float64 polish (above) runs instead
+                                   (cyto_lap_info.exact_status = 3), one problem at a time in a batch.  Not with polish, not on the
+                                   float64 entry points (CYTO_ERR_BAD_ARG).  (the third of the reserved words) */
+    int32_t reserved[2];        /* must be zero */
 } cyto_lap_opts;
 int cyto_lap_f32_opts(int n, const float *cost, int64_t ld, int cost_on_device,
                       int32_t *rowsol, int32_t *colsol, float *u, float *v, double *total,
@@ -201,6 +224,20 @@ int cyto_lap_f32_rowmap(int n, const float *cost_rows, int64_t ld, int nu, int c
  * float32.  The matrix is uploaded as it is and narrowed on the device (same rounding as numpy's astype(float32)). */
 int cyto_lap_f32_from_f64(int n, const double *cost_host, int64_t ld, int32_t *rowsol, int32_t *colsol,
                           float *u, float *v, double *total, cyto_lap_info *info, int device_id, void *stream);
+
+/* The host half of cyto_lap_opts.exact, on its own (no device is touched): the optimum of a sparse assignment problem that contains a
+ * perfect matching, from that matching.
+ *   rowsol[i]            the starting assignment, a permutation of 0 ... n-1
+ *   row_ptr[n + 1], cols, r   row i's edges are cols[row_ptr[i] ... row_ptr[i+1]) with float64 costs r (rowsol[i] among them;
+ *                        missing edges are infinite)
+ *   rowsol_out[i]        the optimum's column of row i (may alias rowsol)
+ * Rows with an edge cheaper than their own are freed; the duals u_i = min_j r_ij, v = 0 are feasible and tight on the rows kept, and
+ * successive shortest paths over the edges (Dijkstra with potentials, float64) re-assign the freed rows: free rows in ascending order,
+ * a binary heap keyed on (distance, column), so equal distances go to the lower column.  A row whose component cannot improve keeps
+ * its column.  CYTO_ERR_BAD_ARG: n <= 0, a null pointer, a column out of range, rowsol not a permutation or not among its row's
+ * edges, a non-finite r. */
+int cyto_lap_repair_sparse(int n, const int32_t *rowsol, const int64_t *row_ptr, const int32_t *cols, const double *r,
+                           int32_t *rowsol_out);
 
 /* ---- A8 (one GPU): nb independent LAPs solved concurrently.  Replaces the per-chunk worker processes of
  * apply_linear_assignment (cytospace/cytospace.py:430-451) for the solver-only seam: the sequential
