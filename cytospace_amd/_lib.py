@@ -148,6 +148,11 @@ def lib():
         L.cyto_lap_batch_f32_opts.restype = ctypes.c_int
         L.cyto_lap_repair_sparse.argtypes = [i32, vp, vp, vp, vp, vp]
         L.cyto_lap_repair_sparse.restype = ctypes.c_int
+        u32p, i32p = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32)
+        L.cyto_downsample.argtypes = [i32, i32, vp, i64, i32, vp, i64, i32, i32, u32p, i32p, ctypes.POINTER(ctypes.c_int64), i32]
+        L.cyto_downsample.restype = ctypes.c_int
+        L.cyto_mt19937_fill.argtypes = [u32p, i32p, i32, u32p, i32]
+        L.cyto_mt19937_fill.restype = ctypes.c_int
         L.cyto_comm_unique_id.argtypes = [ctypes.c_char_p]
         L.cyto_comm_init.argtypes = [ctypes.c_char_p, i32, i32, i32, ctypes.POINTER(vp)]
         L.cyto_comm_init_local.argtypes = [i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(vp)]

@@ -116,6 +116,85 @@ def downsample(data_df, target_count):
     return pd.DataFrame(out, index=index, columns=data_df.columns)
 
 
+# upload codes of cyto_downsample (CYTO_DTYPE_*); other integer dtypes are widened on the host first
+_DS_IN = {np.dtype(np.uint8): 3, np.dtype(np.uint16): 2, np.dtype(np.int32): 4, np.dtype(np.int64): 5}
+_DS_WIDEN = {np.dtype(np.bool_): np.uint8, np.dtype(np.int8): np.int32, np.dtype(np.int16): np.int32, np.dtype(np.uint32): np.int64}
+
+
+def downsample_device(data_df, target_count, device_id=0, dtype=np.int64, return_words=False):
+    """`downsample` on the GPU (C ABI: cyto_downsample): the same DataFrame -- index, columns, values -- and the same
+    global numpy RandomState afterwards (np.random.set_state keeps has_gauss and the cached value), for the same state
+    before.  The draws follow numpy's legacy MT19937 stream and masked rejection sampling word for word.
+
+    dtype: np.int64 (default) or np.uint16 (target_count < 65536 and no negative count: every value is then at most
+    target_count).  return_words: also return the number of raw MT19937 words consumed.  Raises TypeError for a non-integer matrix (np.repeat refuses it) and ValueError, before any draw,
+    for a negative count in a cell that is downsampled or a cell total above 2^32."""
+    import pandas as pd
+    x = data_df.to_numpy()
+    if x.dtype.kind not in "biu" or x.dtype == np.uint64:
+        raise TypeError(f"Cannot downsample counts of dtype {x.dtype}: an integer count matrix is required")
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.int64), np.dtype(np.uint16)):
+        raise ValueError("dtype must be np.int64 or np.uint16")
+    target = int(target_count)
+    if target < 0:
+        raise ValueError("target_count must be non-negative")
+    if dtype == np.uint16 and target > 65535:
+        raise ValueError("dtype=np.uint16 needs target_count < 65536")
+    if target > 2**31 - 1:
+        raise ValueError("target_count must be below 2^31")
+    G, C = x.shape
+    if G == 0 or C == 0:
+        df = pd.DataFrame(x.astype(dtype), index=data_df.index, columns=data_df.columns)
+        return (df, 0) if return_words else df
+    if x.dtype in _DS_WIDEN:
+        x = x.astype(_DS_WIDEN[x.dtype])
+    x = np.ascontiguousarray(x)
+    state = np.random.get_state()
+    if state[0] != "MT19937":
+        raise ValueError("numpy's global generator is not MT19937")
+    key = np.array(state[1], dtype=np.uint32)
+    pos = ctypes.c_int32(int(state[2]))
+    words = ctypes.c_int64()
+    out = np.empty((G, C), dtype)
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    st = _lib.lib().cyto_downsample(G, C, x.ctypes.data, C, _DS_IN[x.dtype], out.ctypes.data, C, 5 if dtype == np.int64 else 2, target,
+                                    key.ctypes.data_as(u32p), ctypes.byref(pos), ctypes.byref(words), device_id)
+    if st == 1:
+        raise ValueError("cannot downsample: a cell with more than target_count transcripts holds a negative count or more than "
+                         "2^32 transcripts" + (" (or, with dtype=np.uint16, some count is negative)" if dtype == np.uint16 else ""))
+    _lib.check(st)
+    np.random.set_state(("MT19937", key, pos.value, state[3], state[4]))
+    df = pd.DataFrame(out, index=data_df.index, columns=data_df.columns)
+    return (df, words.value) if return_words else df
+
+
+def mt19937_fill(n, device_id=0):
+    """The next n raw 32-bit words of numpy's global legacy stream, generated on the GPU (C ABI: cyto_mt19937_fill, the
+    generator of downsample_device alone); numpy's global state is advanced past them, as
+    np.random.randint(0, 2**32, n, dtype=np.uint32) would advance it."""
+    state = np.random.get_state()
+    key = np.array(state[1], dtype=np.uint32)
+    pos = ctypes.c_int32(int(state[2]))
+    out = np.empty(int(n), np.uint32)
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    _lib.check(_lib.lib().cyto_mt19937_fill(key.ctypes.data_as(u32p), ctypes.byref(pos), int(n), out.ctypes.data_as(u32p), device_id))
+    np.random.set_state(("MT19937", key, pos.value, state[3], state[4]))
+    return out
+
+
+def check_paths(output_folder, output_prefix):
+    """cytospace/common/common.py:176-187: the output folder (relative to the working directory) is created if needed; a
+    warning is printed when results with this prefix would be overwritten.  Returns its absolute path."""
+    import os
+    output_path = os.path.join(os.getcwd(), output_folder)
+    os.makedirs(output_path, exist_ok=True)
+    if os.path.exists(os.path.join(output_path, f"{output_prefix}assigned_locations.csv")):
+        print("\033[91mWARNING\033[0m: Running this will overwrite previous results, choose a new"
+              " 'output_folder' or 'output_prefix'")
+    return output_path
+
+
 class StandardizedMatrix:
     """A gene x column matrix as the float32 GEMM operand of a metric, zero padded, resident in HBM:
     standardised values (Pearson), standardised average-tie ranks (Spearman) or the plain values (Euclidean)."""

@@ -631,3 +631,243 @@ def sample_single_cells(scRNA_data, cell_type_data, cell_type_numbers_int, sampl
     if sampling_method == "place_holders":
         return pd.DataFrame(np.concatenate(blocks, axis=1), index=scRNA_data.index, columns=np.concatenate(names, axis=0))
     return scRNA_data.iloc[:, np.concatenate(picked, axis=0).astype(int)]
+
+
+# ---- the driver (cytospace/cytospace.py:20-113, 472-717): files in, results out.  Host code like the reference's; the
+# heavy steps (downsampling, the per-spot estimate's normalisation, every chunk's cost build and LAP) run on the GPU. ----
+
+def read_data(scRNA_path, cell_type_path, cell_type_fraction_estimation_path, n_cells_per_spot_path,
+              st_cell_type_path, output_path, output_prefix, spaceranger_path=None, st_path=None, coordinates_path=None):
+    """cytospace.py:20-113.  Reads the inputs and prefixes their ids (spots 'SPOT_', cells 'CELL_', genes 'GENE_', cell
+    types 'TYPE_'), drops genes listed more than once, orders ST and scRNA columns like the coordinates and cell-type
+    tables, and validates.  A MatrixMarket input is read dense, as the reference reads it.  Unlike the reference this
+    never reads a Space Ranger archive or estimates fractions with R: both raise ValueError (see check_supported)."""
+    from .common import read_file
+    check_supported(spaceranger_path=spaceranger_path, st_cell_type_path=st_cell_type_path,
+                    cell_type_fraction_estimation_path=cell_type_fraction_estimation_path)
+    if (st_path is None) and (coordinates_path is None):
+        raise ValueError("For ST data, you must provide either a tar.gz file or paths for expression and coordinates.")
+
+    def read(path):
+        return read_file(path, keep_sparse=False)
+
+    st_data = read(st_path)
+    coordinates_data = read(coordinates_path)
+    st_data = st_data[~st_data.index.duplicated(keep=False)]
+    st_data.columns = ["SPOT_" + str(c) for c in st_data.columns]
+    st_data.index = ["GENE_" + str(g) for g in st_data.index]
+    coordinates_data.index = ["SPOT_" + str(s) for s in coordinates_data.index]
+
+    scRNA_data = read(scRNA_path)
+    scRNA_data.columns = ["CELL_" + str(c) for c in scRNA_data.columns]
+    scRNA_data.index = ["GENE_" + str(g) for g in scRNA_data.index]
+    scRNA_data = scRNA_data[~scRNA_data.index.duplicated(keep=False)]
+
+    cell_type_data = read(cell_type_path)
+    cell_type_data.index = ["CELL_" + str(c) for c in cell_type_data.index]
+    cell_type_data.iloc[:, 0] = ["TYPE_" + str(t) for t in cell_type_data.iloc[:, 0]]
+
+    st_cell_type_data = None
+    if st_cell_type_path is not None:
+        st_cell_type_data = read(st_cell_type_path)
+        st_cell_type_data.index = ["SPOT_" + str(s) for s in st_cell_type_data.index]
+        st_cell_type_data.iloc[:, 0] = ["TYPE_" + str(t) for t in st_cell_type_data.iloc[:, 0]]
+    cell_type_fraction_data = None
+    if cell_type_fraction_estimation_path is not None:
+        cell_type_fraction_data = read(cell_type_fraction_estimation_path)
+        cell_type_fraction_data.columns = ["TYPE_" + str(t) for t in cell_type_fraction_data.columns]
+    n_cells_per_spot_data = None
+    if n_cells_per_spot_path is not None:
+        n_cells_per_spot_data = read(n_cells_per_spot_path)
+        n_cells_per_spot_data.index = ["SPOT_" + str(s) for s in n_cells_per_spot_data.index]
+
+    try:
+        st_data = st_data[coordinates_data.index]
+        scRNA_data = scRNA_data[cell_type_data.index]
+        if st_cell_type_data is not None:
+            st_cell_type_data = st_cell_type_data.loc[coordinates_data.index, :]
+        if n_cells_per_spot_data is not None:
+            n_cells_per_spot_data = n_cells_per_spot_data.transpose(copy=False)[coordinates_data.index].transpose(copy=False)
+    except Exception:
+        raise IndexError(f"The ST data: {st_path} and coordinates data: {coordinates_path} have to "
+                         "have the same spot IDs for columns and rows, respectively, "
+                         f"and scRNA data: {scRNA_path} and cell type data: {cell_type_path} have"
+                         " to have the same cell IDs for columns and rows, respectively.")
+    if (st_data.columns != coordinates_data.index).any():
+        raise IndexError(f"The ST data: {st_path} and coordinates data: {coordinates_path} have to "
+                         "have the same spot IDs for columns and rows, respectively.")
+    if (scRNA_data.columns != cell_type_data.index).any():
+        raise IndexError(f"The scRNA data: {scRNA_path} and cell type data: {cell_type_path} have"
+                         " to have the same cell IDs for columns and rows, respectively.")
+    if (st_cell_type_data is not None) and (st_cell_type_data.index != coordinates_data.index).any():
+        raise IndexError(f"The ST cell type data: {st_cell_type_path} and coordinates data: {coordinates_path} have to "
+                         "have the same spot IDs for rows.")
+    if (st_cell_type_data is not None) and (cell_type_fraction_data is not None):
+        print("Warning: st_cell_type_path and cell_type_fraction_estimation_path are both specified.")
+        print("If --single-cell, cell_type_fraction_estimation_path will be ignored in this case.")
+    return scRNA_data, cell_type_data, st_data, coordinates_data, cell_type_fraction_data, n_cells_per_spot_data, st_cell_type_data
+
+
+def check_supported(solver_method="lapjv_hip", spaceranger_path=None, st_cell_type_path=None,
+                    cell_type_fraction_estimation_path=None):
+    """The reference's paths this package does not take, refused with a ValueError before any file or device is touched:
+    a Space Ranger archive (the reference reads it with scanpy), cell type fractions estimated in R (the reference spawns
+    Rscript when neither fraction file is given) and any solver but lapjv_hip (the only one apply_linear_assignment drives)."""
+    if spaceranger_path is not None:
+        raise ValueError("--spaceranger-path is not supported here (it needs scanpy): pass -stp (ST expression) and -cp "
+                         "(coordinates) instead")
+    if (st_cell_type_path is None) and (cell_type_fraction_estimation_path is None):
+        raise ValueError("Either -ctfep (cell type fractions) or -stctp (ST cell types) is required here: estimating cell type "
+                         "fractions needs R, which this package does not run")
+    if solver_method != "lapjv_hip":
+        raise ValueError(f"solver_method {solver_method!r} is not supported by main_cytospace here: the assignment runs on "
+                         "the GPU solver, choose 'lapjv_hip'")
+
+
+def main_cytospace(scRNA_path, cell_type_path,
+                   n_cells_per_spot_path, st_cell_type_path, cell_type_fraction_estimation_path=None,
+                   spaceranger_path=None, st_path=None, coordinates_path=None,
+                   output_folder="cytospace_results", output_prefix="",
+                   mean_cell_numbers=5, downsample_off=False, scRNA_max_transcripts_per_cell=1500,
+                   solver_method="lapjv_hip", distance_metric="Pearson_correlation", sampling_method="duplicates",
+                   single_cell=False, number_of_selected_spots=10000,
+                   sampling_sub_spots=False, number_of_selected_sub_spots=10000,
+                   number_of_processors=1, seed=1,
+                   plot_off=False, geometry="honeycomb", max_num_cells_plot=50000, num_column=3, devices=None):
+    """cytospace.py:472-717 with the same arguments (plus `devices`, see apply_linear_assignment) and the same random-number
+    use: both generators seeded, then cells per spot, cell type numbers, the gene intersection, the downsampling (on the GPU,
+    the same draws as the host's), sample_single_cells and the partitions; then every chunk on the GPU solver and the
+    reference's output files and log.  Plots are not produced (the plotting arguments are accepted and logged)."""
+    import random
+    import pandas as pd
+    from .common import check_paths, downsample_device
+    from .post_processing import save_results, save_unassigned_locations
+
+    check_supported(solver_method, spaceranger_path, st_cell_type_path, cell_type_fraction_estimation_path)
+    start_time = time.perf_counter()
+    output_path = check_paths(output_folder, output_prefix)
+    fout_log = os.path.join(output_path, f"{output_prefix}log.txt")
+    args = [("scRNA_path", scRNA_path), ("cell_type_path", cell_type_path), ("st_path", st_path),
+            ("coordinates_path", coordinates_path), ("n_cells_per_spot_path", n_cells_per_spot_path),
+            ("cell_type_fraction_estimation_path", cell_type_fraction_estimation_path), ("st_cell_type_path", st_cell_type_path),
+            ("output_folder", output_folder), ("mean_cell_numbers", mean_cell_numbers), ("downsample_off", downsample_off),
+            ("scRNA_max_transcripts_per_cell", scRNA_max_transcripts_per_cell), ("plot_off", plot_off), ("geometry", geometry),
+            ("output_prefix", output_prefix), ("seed", seed), ("solver_method", solver_method),
+            ("sampling_method", sampling_method), ("distance_metric", distance_metric)]
+    with open(fout_log, "w") as f:
+        f.write("CytoSPACE log file \n\nStart time: " + str(time.asctime(time.localtime(time.time()))) + "\n")
+        f.write("\nINPUT ARGUMENTS\n")
+        for name, value in args:
+            f.write(f"{name}: {value}\n")
+        f.write(f"single_cell: {single_cell}\n\n")
+        f.write(f"sampling_sub_spots: {sampling_sub_spots}\n\n")
+
+    def log(line):
+        with open(fout_log, "a") as f:
+            f.write(line)
+
+    print("Read and validate data ...")
+    t0 = time.perf_counter()
+    scRNA_data, cell_type_data, st_data, coordinates_data, cell_type_fractions_data, n_cells_per_spot_data, st_cell_type_data = \
+        read_data(scRNA_path, cell_type_path, cell_type_fraction_estimation_path, n_cells_per_spot_path, st_cell_type_path,
+                  output_path, output_prefix, spaceranger_path, st_path, coordinates_path)
+    all_spot_ids = st_data.columns
+    print(f"Time to read and validate data: {round(time.perf_counter() - t0, 2)} seconds")
+    log(f"Time to read and validate data: {round(time.perf_counter() - t0, 2)} seconds\n")
+    device = visible_devices(devices)[0]
+
+    np.random.seed(seed)
+    random.seed(seed)
+    t0_core = time.perf_counter()
+
+    if single_cell:
+        cell_number_to_node_assignment = np.ones(st_data.shape[1]).astype(int)
+    elif n_cells_per_spot_data is None:
+        print("Estimating number of cells in each spot ...")
+        cell_number_to_node_assignment = estimate_cell_number_RNA_reads(st_data, mean_cell_numbers, device)
+        print(f"Time to estimate number of cells per spot: {round(time.perf_counter() - t0_core, 2)} seconds")
+    else:
+        cell_number_to_node_assignment = n_cells_per_spot_data.values[:, 0].astype(int)
+
+    if single_cell and (st_cell_type_data is not None):
+        cell_types = sorted(st_cell_type_data.iloc[:, 0].unique(), key=str.lower)
+        cell_type_numbers_int = pd.DataFrame(st_cell_type_data.iloc[:, 0].value_counts().reindex(cell_types))
+        cell_type_numbers_int.columns = ["Fraction"]
+    else:
+        if cell_type_fractions_data is None:
+            raise ValueError("cell_type_fraction_estimation_path must be specified.")
+        cell_type_numbers_int = get_cell_type_fraction(np.sum(cell_number_to_node_assignment), cell_type_fractions_data)
+        # the reference's column ends up int64 (pandas upcasts on its 2-D assignment); sample_single_cells needs integers
+        cell_type_numbers_int = cell_type_numbers_int.astype(np.int64)
+
+    print("Down/up sample of scRNA-seq data according to estimated cell type fractions")
+    t0 = time.perf_counter()
+    intersect_genes = st_data.index.intersection(scRNA_data.index)
+    scRNA_data_sampled = scRNA_data.loc[intersect_genes, :]
+    st_data = st_data.loc[intersect_genes, :]
+    if not downsample_off:
+        scRNA_data_sampled = downsample_device(scRNA_data_sampled, scRNA_max_transcripts_per_cell, device_id=device)
+    log("Number of genes used for mapping: " + str(len(intersect_genes)) + "\n")
+    log("Number of spots satisfying input for mapping: " + str(st_data.shape[1]) + "\n")
+    log("Number of cells satisfying input for mapping: " + str(scRNA_data_sampled.shape[1]) + "\n")
+    scRNA_data_sampled = sample_single_cells(scRNA_data_sampled, cell_type_data, cell_type_numbers_int, sampling_method, seed)
+    print(f"Time to down/up sample scRNA-seq data: {round(time.perf_counter() - t0, 2)} seconds")
+
+    n_cells = scRNA_data_sampled.shape[1]
+    fan = dict(devices=devices)
+    if single_cell:
+        log(f"Number of selected spots: {number_of_selected_spots}\n\n")
+        log(f"Number of processors: {number_of_processors}\n\n")
+        if st_cell_type_data is not None:
+            per_type = cell_type_numbers_int.values.flatten()
+            index_sc_list = partition_indices(np.arange(n_cells), split_by_category_list=per_type,
+                                              split_by_interval_int=number_of_selected_spots, shuffle=False)
+            order = np.concatenate([np.where(st_cell_type_data.values[:, 0] == t)[0] for t in cell_type_numbers_int.index], axis=0)
+            index_st_list = partition_indices(order, split_by_category_list=per_type,
+                                              split_by_interval_int=number_of_selected_spots, shuffle=False)
+        else:
+            index_sc_list = partition_indices(np.arange(n_cells), split_by_interval_int=number_of_selected_spots, shuffle=True)
+            index_st_list = partition_indices(np.arange(st_data.shape[1]), split_by_interval_int=number_of_selected_spots,
+                                              shuffle=True)
+        assigned_locations, cell_ids_selected = apply_linear_assignment(
+            scRNA_data_sampled, st_data, coordinates_data, cell_number_to_node_assignment, solver_method, None, seed,
+            distance_metric, number_of_processors, index_sc_list, index_st_list=index_st_list, **fan)
+    elif sampling_sub_spots:
+        log(f"Number of selected subspots: {number_of_selected_sub_spots}\n\n")
+        log(f"Number of processors: {number_of_processors}\n\n")
+        if number_of_selected_sub_spots > np.sum(cell_number_to_node_assignment):
+            number_of_selected_sub_spots = np.sum(cell_number_to_node_assignment)
+        index_sc_list = partition_indices(np.arange(n_cells), split_by_interval_int=number_of_selected_sub_spots, shuffle=True)
+        spot_of_slot = np.repeat(range(len(cell_number_to_node_assignment)), cell_number_to_node_assignment)
+        sub_lists = partition_indices(spot_of_slot, split_by_interval_int=number_of_selected_sub_spots, shuffle=True)
+        sub_slots = [np.bincount(ix, minlength=len(cell_number_to_node_assignment)) for ix in sub_lists]
+        assigned_locations, cell_ids_selected = apply_linear_assignment(
+            scRNA_data_sampled, st_data, coordinates_data, cell_number_to_node_assignment, solver_method, None, seed,
+            distance_metric, number_of_processors, index_sc_list, subsampled_cell_number_to_node_assignment_list=sub_slots, **fan)
+    else:
+        index_sc_list = partition_indices(np.arange(n_cells), shuffle=False)
+        assigned_locations, cell_ids_selected = apply_linear_assignment(
+            scRNA_data_sampled, st_data, coordinates_data, cell_number_to_node_assignment, solver_method, None, seed,
+            distance_metric, number_of_processors, index_sc_list, **fan)
+
+    print(f"Total time to run CytoSPACE core algorithm: {round(time.perf_counter() - t0_core, 2)} seconds")
+    log(f"Time to run CytoSPACE core algorithm: {round(time.perf_counter() - t0_core, 2)} seconds\n")
+
+    print("Saving results ...")
+    n_unmapped = save_unassigned_locations(output_path, output_prefix, all_spot_ids, assigned_locations, coordinates_data)
+    if n_unmapped > 0:
+        print(f"{n_unmapped} spots had no cells mapped to them. Saved unfiltered version of assigned locations to "
+              f"{output_path}/{output_prefix}unassigned_locations.csv")
+    save_results(output_path, output_prefix, cell_ids_selected,
+                 scRNA_data_sampled if sampling_method == "place_holders" else scRNA_data,
+                 assigned_locations, cell_type_data, sampling_method, single_cell)
+    if not plot_off:
+        print("Plotting is not part of this package: no plots are produced (the results are written as files).")
+    print(f"Total execution time: {round(time.perf_counter() - start_time, 2)} seconds")
+    log(f"Total execution time: {round(time.perf_counter() - start_time, 2)} seconds")
+
+
+def run_cytospace(argv=None):
+    """The `cytospace` command line (python -m cytospace_amd ...)."""
+    from .argument_parser import argument_parser
+    main_cytospace(**argument_parser(argv))

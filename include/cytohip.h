@@ -282,7 +282,8 @@ int cyto_comm_destroy(void *comm);
 /* ---- element types of the expression matrices at this boundary.  Every `x_is_f64` parameter below and cyto_matrix.is_f64 carry one
  * of these (0 and 1 mean what the name says; 2 and 3 came in round 6): raw counts are small integers, and a uint16 / uint8 matrix is a
  * half / a quarter of the float32 upload -- the transform kernels widen in their loads, the numbers are the same bit for bit. */
-enum { CYTO_DTYPE_F32 = 0, CYTO_DTYPE_F64 = 1, CYTO_DTYPE_U16 = 2, CYTO_DTYPE_U8 = 3 };
+enum { CYTO_DTYPE_F32 = 0, CYTO_DTYPE_F64 = 1, CYTO_DTYPE_U16 = 2, CYTO_DTYPE_U8 = 3, CYTO_DTYPE_I32 = 4, CYTO_DTYPE_I64 = 5 };
+/* (CYTO_DTYPE_I32 / _I64: integer count matrices of cyto_downsample only) */
 
 /* ---- A1: normalize_data (cytospace/common/common.py:142-147): nan_to_num, per-column counts per
  * million over the gene axis, log2(x + 1), nan_to_num.  x: G x C host matrix (float64 if x_is_f64
@@ -406,6 +407,20 @@ int cyto_ctx_create_typed(int metric, int G, int C, int S, const void *sc, const
  * what cytospace_amd.cytospace.assign_pearson passes for integer count matrices (config c3: the upload bounds the call). */
 int cyto_assign_metric_ex(int metric, int G, const cyto_matrix *sc, int C, const cyto_matrix *st, int S, const int64_t *slots,
                           int already_normalized, int64_t *mapped_spot, double *total_cost, cyto_assign_info *info, int device_id);
+
+/* ---- downsample (cytospace/common/common.py:149-173): every cell (column) whose total T exceeds `target` is replaced by the
+ * histogram of `target` draws with replacement from its transcripts, with exactly the words numpy's legacy global RandomState
+ * (MT19937) would use: per draw, 32-bit words w until (w & mask) <= T-1, mask = 2^bitlength(T-1) - 1; cells in column order;
+ * cells with T <= target are copied and take no words.  x: G x C host matrix (ldx) of CYTO_DTYPE_U8 / _U16 / _I32 / _I64;
+ * out: G x C host matrix (ldo) of CYTO_DTYPE_I64 or CYTO_DTYPE_U16 (target <= 65535, no negative count anywhere).
+ * key[624] / *pos: numpy's state (get_state()[1:3]) in, the state after the last consumed word out (pos == 624 when that word
+ * ends the key: the twist is deferred, as numpy defers it).  *words_out (may be NULL): raw words consumed.
+ * CYTO_ERR_BAD_ARG, before any word is drawn: a negative count in a cell that is downsampled (np.repeat's ValueError), a
+ * downsampled cell with T > 2^32 when target > 0 (numpy draws 64-bit words there), a bad dtype or size. */
+int cyto_downsample(int G, int C, const void *x, int64_t ldx, int x_dtype, void *out, int64_t ldo, int out_dtype, int target,
+                    uint32_t *key, int32_t *pos, int64_t *words_out, int device_id);
+/* The generator alone (a test hook): the next n raw 32-bit MT19937 words from (key, *pos), with the state after them. */
+int cyto_mt19937_fill(uint32_t *key, int32_t *pos, int n, uint32_t *words, int device_id);
 
 #ifdef __cplusplus
 }
