@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round-end measurement set: the default bench line; rocprofv3 kernel stats + trace of the same command (headline only: n = 50 000, and
+# Round-end measurement set: the full bench line (--full); rocprofv3 kernel stats + trace of the same command (headline only: n = 50 000, and
 # n = 20 000; with the extra legs: stats only); PMC traffic passes (FETCH_SIZE / WRITE_SIZE, each in its own run, with --kernel-trace
 # only) of one LAP at n = 20 000, n = 50 000 and of the few-cell-type 20 000 instance; PMC pass of the c3-sized cost GEMM.
 # Usage (gpurun): bash tools/prof_round.sh r06 ; then tools/prof_collect.sh r06 copies the summaries into profiles/
@@ -7,11 +7,11 @@
 TAG=${1:-r06}
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/$TAG; mkdir -p $OUT
-python $R/bench.py > $OUT/bench.json 2> $OUT/bench.err
+python $R/bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 for n in 50000 20000; do
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_n$n -o n$n -- python $R/bench.py --n $n --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $OUT/prof_n$n.log 2>&1
 done
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_extras -o extras -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline > $OUT/prof_extras.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_extras -o extras -- python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline > $OUT/prof_extras.log 2>&1
 for n in 20000 50000; do
   mkdir -p $OUT/pmc_n$n
   rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_n$n -o fetch -- python $R/tools/quick_lap_bench.py $n > $OUT/pmc_n$n/fetch.log 2>&1
