@@ -153,6 +153,15 @@ def lib():
         L.cyto_downsample.restype = ctypes.c_int
         L.cyto_mt19937_fill.argtypes = [u32p, i32p, i32, u32p, i32]
         L.cyto_mt19937_fill.restype = ctypes.c_int
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        L.cyto_table_read.argtypes = [ctypes.c_char_p, ctypes.c_char, i64, i64, i32, ctypes.POINTER(vp), i64p, i64p, dp]
+        L.cyto_table_read.restype = ctypes.c_int
+        L.cyto_table_fetch.argtypes = [vp, vp, vp, vp, dp]
+        L.cyto_table_fetch.restype = ctypes.c_int
+        L.cyto_table_free.argtypes = [vp]
+        L.cyto_table_free.restype = None
+        L.cyto_table_parse_tokens.argtypes = [vp, i64, vp, vp, vp, vp]
+        L.cyto_table_parse_tokens.restype = ctypes.c_int
         L.cyto_comm_unique_id.argtypes = [ctypes.c_char_p]
         L.cyto_comm_init.argtypes = [ctypes.c_char_p, i32, i32, i32, ctypes.POINTER(vp)]
         L.cyto_comm_init_local.argtypes = [i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(vp)]

@@ -99,6 +99,138 @@ def read_file(file_path, keep_sparse=True):
     return pd.read_csv(file_path, sep=sep, header=0, index_col=0)
 
 
+# why cyto_table_read refused a file (CYTO_TABLE_ERR_*): read_file_device's info["reason"]["kind"]
+_TABLE_REFUSALS = {1: "io", 2: "control byte", 3: "quote", 4: "carriage return", 5: "blank line", 6: "field count", 7: "token",
+                   8: "out of range", 9: "integer cast in a float column"}
+_COMPRESSED = (".gz", ".bz2", ".zip", ".xz", ".zst", ".tar")
+# a row label that pandas would not keep as text (a number, inf / nan, a boolean): in an object index it may come out as text here
+# but as a number in pandas' own read, which infers types per block of rows
+_NOT_TEXT = r"\s*[+-]?(?:(?:\d+\.?\d*|\.\d+)(?:[eE][+-]?\d+)?|inf|infinity|nan)\s*|true|false"
+# an integer label whose value may differ between a block of rows read as int64 and one read as float64 (17+ digits, "-0")
+_CAST_LABEL = r"\s*[+-]?\d{17,}\s*|\s*-0+\s*"
+
+
+def _table_on_device(file_path, device_id, info):
+    """read_file_device's device path: the DataFrame, or None (info["reason"] says why) for a file outside its grammar."""
+    import io
+    import time
+    import pandas as pd
+
+    def refuse(kind, line=0, byte=0):
+        info["reason"] = {"kind": kind, "line": int(line), "byte": int(byte)}
+        return None
+    if not isinstance(file_path, str):
+        return refuse("not a path")
+    low = file_path.lower()
+    if file_path.endswith(".mtx") or file_path.endswith(".mtx.gz"):
+        return refuse("matrix market")
+    if low.endswith(_COMPRESSED):
+        return refuse("compressed")
+    sep = "," if low.endswith(".csv") else "\t"
+    try:
+        with open(file_path, "rb") as f:
+            header, first = f.readline(), f.readline()
+    except OSError:
+        return refuse("io")
+    # the header goes to pandas as it is; it must be one line to pandas too (no '\r' but before its '\n', no open quote)
+    name_line = header[:-2] if header.endswith(b"\r\n") else header[:-1]
+    if not header.endswith(b"\n") or not name_line.strip() or b"\r" in name_line or name_line.count(b'"') % 2 or \
+            any(b < 0x20 and b != ord(sep) for b in name_line):
+        return refuse("header", 1)
+    C = first.count(sep.encode())
+    if C == 0:
+        return refuse("no data columns", 2)
+    t = time.perf_counter()
+    try:                                    # the header with the first data line: pandas decides between the two header shapes
+        head = pd.read_csv(io.BytesIO(header + first), sep=sep, header=0, index_col=0)
+    except Exception:
+        return refuse("header", 1)
+    if head.shape[1] != C or isinstance(head.index, pd.MultiIndex):
+        return refuse("header", 1)
+    info["header_s"] = time.perf_counter() - t
+    L = _lib.lib()
+    h = ctypes.c_void_p()
+    shape, why = (ctypes.c_int64 * 3)(), (ctypes.c_int64 * 3)()
+    ms, ms_dl = (ctypes.c_double * 3)(), ctypes.c_double()
+    t = time.perf_counter()
+    st = L.cyto_table_read(file_path.encode(), sep.encode(), len(header), C, device_id, ctypes.byref(h), shape, why, ms)
+    call = time.perf_counter() - t
+    info.update(file_read_s=ms[0] / 1e3, upload_s=ms[1] / 1e3, kernels_s=ms[2] / 1e3)
+    info["device_setup_s"] = max(0.0, call - (ms[0] + ms[1] + ms[2]) / 1e3)     # allocations, pinned buffers, their release
+    if st == 7:                                                              # CYTO_ERR_UNSUPPORTED
+        return refuse(_TABLE_REFUSALS.get(why[0], str(why[0])), why[1], why[2])
+    _lib.check(st)
+    try:
+        G, C, nlab = shape
+        values = np.empty((G, C), np.int64)
+        is_float = np.empty(C, np.int8)
+        labels = np.empty(nlab, np.uint8)
+        _lib.check(L.cyto_table_fetch(h, values.ctypes.data, is_float.ctypes.data, labels.ctypes.data, ctypes.byref(ms_dl)))
+    finally:
+        t = time.perf_counter()
+        L.cyto_table_free(h)
+        info["free_s"] = time.perf_counter() - t
+    info["download_s"] = ms_dl.value / 1e3
+    t = time.perf_counter()
+    # the row labels, handed back to pandas as a table of their own: its inference (integers, NA, ...), duplicates kept
+    index = pd.read_csv(io.BytesIO(labels.tobytes()), sep=sep, header=None, index_col=0).index
+    if index.dtype == object and pd.Series(index.astype(str)).str.fullmatch(_NOT_TEXT, case=False).any():
+        return refuse("row labels")
+    if index.dtype.kind in "fu" and pd.Series(labels.tobytes().decode("utf-8", "replace").split(sep + "\n")[:-1]).str.fullmatch(
+            _CAST_LABEL).any():
+        return refuse("row labels")
+    index = index.rename(head.index.name)
+    f = is_float.astype(bool)
+    if not f.any():
+        df = pd.DataFrame(values, index=index, columns=head.columns, copy=False)
+    elif f.all():
+        df = pd.DataFrame(values.view(np.float64), index=index, columns=head.columns, copy=False)
+    else:
+        df = pd.concat([pd.DataFrame(values[:, ~f]), pd.DataFrame(values[:, f].view(np.float64))], axis=1, ignore_index=True)
+        df = df.iloc[:, np.argsort(np.concatenate([np.flatnonzero(~f), np.flatnonzero(f)]), kind="stable")]
+        df.index, df.columns = index, head.columns
+    info["dataframe_s"] = time.perf_counter() - t
+    return df
+
+
+def read_file_device(file_path, device_id=0, return_info=False):
+    """read_file(file_path, keep_sparse=False) for a dense delimited text table (.csv: ','; otherwise tab), parsed on the GPU
+    (C ABI: cyto_table_read / cyto_table_fetch; csrc/table.hip).  The result is equal to read_file's: index, columns (pandas'
+    header parse, duplicates mangled), every column's dtype (int64 or float64) and every value bit for bit (pandas' own decimal
+    converter).  A file outside the grammar of DESIGN.md 4.1c -- quotes, NA or empty values, ragged or blank lines, integers of 19+
+    digits, values beyond float64, MatrixMarket, compressed files, no data columns -- is read by read_file itself: its result, or
+    its exception.
+
+    return_info: also return a dict -- "path" ("device" or "pandas"), for a fallback "reason" {"kind", "line", "byte"}, and the
+    phase times in seconds: header_s (pandas' parse of the header), file_read_s, upload_s (what the upload added to the reads),
+    kernels_s, device_setup_s (the rest of the device call: allocations, pinned buffers, their release), download_s, free_s,
+    dataframe_s (the row labels' parse and the DataFrame), total_s."""
+    import time
+    t = time.perf_counter()
+    info = {"path": "device"}
+    df = _table_on_device(file_path, device_id, info)
+    if df is None:
+        info["path"] = "pandas"
+        df = read_file(file_path, keep_sparse=False)
+    info["total_s"] = time.perf_counter() - t
+    return (df, info) if return_info else df
+
+
+def parse_table_tokens(tokens):
+    """The device reader's token converter, run on the host (C ABI: cyto_table_parse_tokens, a test hook).  tokens: a list of
+    str.  Returns (kind, value, ints): kind 0 integer token, 1 decimal token, 2 outside the token grammar, 3 out of range; value
+    the float64 as the converter gives it (kinds 0 and 1); ints the int64 value (kind 0)."""
+    raw = [t.encode() for t in tokens]
+    text = b"".join(raw)
+    off = np.zeros(len(raw) + 1, np.int64)
+    np.cumsum([len(r) for r in raw], out=off[1:])
+    n = len(raw)
+    kind, value, ints = np.empty(n, np.int8), np.empty(n, np.float64), np.empty(n, np.int64)
+    buf = ctypes.create_string_buffer(text, len(text) + 1)
+    _lib.check(_lib.lib().cyto_table_parse_tokens(buf, n, off.ctypes.data, value.ctypes.data, ints.ctypes.data, kind.ctypes.data))
+    return kind, value, ints
+
+
 def downsample(data_df, target_count):
     """cytospace/common/common.py:149-173.  Every cell (column) with more than target_count transcripts is reduced to
     target_count draws WITH replacement from its transcripts (np.random.choice over the expanded gene list, legacy

@@ -637,12 +637,15 @@ def sample_single_cells(scRNA_data, cell_type_data, cell_type_numbers_int, sampl
 # heavy steps (downsampling, the per-spot estimate's normalisation, every chunk's cost build and LAP) run on the GPU. ----
 
 def read_data(scRNA_path, cell_type_path, cell_type_fraction_estimation_path, n_cells_per_spot_path,
-              st_cell_type_path, output_path, output_prefix, spaceranger_path=None, st_path=None, coordinates_path=None):
+              st_cell_type_path, output_path, output_prefix, spaceranger_path=None, st_path=None, coordinates_path=None,
+              device_id=0):
     """cytospace.py:20-113.  Reads the inputs and prefixes their ids (spots 'SPOT_', cells 'CELL_', genes 'GENE_', cell
     types 'TYPE_'), drops genes listed more than once, orders ST and scRNA columns like the coordinates and cell-type
-    tables, and validates.  A MatrixMarket input is read dense, as the reference reads it.  Unlike the reference this
-    never reads a Space Ranger archive or estimates fractions with R: both raise ValueError (see check_supported)."""
-    from .common import read_file
+    tables, and validates.  The two expression tables (scRNA_path, st_path), when they are delimited text, are parsed on GPU
+    device_id by common.read_file_device (the same DataFrames as read_file; a file outside its grammar is read by read_file);
+    the small tables are read by read_file.  A MatrixMarket input is read dense, as the reference reads it.  Unlike the
+    reference this never reads a Space Ranger archive or estimates fractions with R: both raise ValueError (see check_supported)."""
+    from .common import read_file, read_file_device
     check_supported(spaceranger_path=spaceranger_path, st_cell_type_path=st_cell_type_path,
                     cell_type_fraction_estimation_path=cell_type_fraction_estimation_path)
     if (st_path is None) and (coordinates_path is None):
@@ -651,14 +654,14 @@ def read_data(scRNA_path, cell_type_path, cell_type_fraction_estimation_path, n_
     def read(path):
         return read_file(path, keep_sparse=False)
 
-    st_data = read(st_path)
+    st_data = read_file_device(st_path, device_id)
     coordinates_data = read(coordinates_path)
     st_data = st_data[~st_data.index.duplicated(keep=False)]
     st_data.columns = ["SPOT_" + str(c) for c in st_data.columns]
     st_data.index = ["GENE_" + str(g) for g in st_data.index]
     coordinates_data.index = ["SPOT_" + str(s) for s in coordinates_data.index]
 
-    scRNA_data = read(scRNA_path)
+    scRNA_data = read_file_device(scRNA_path, device_id)
     scRNA_data.columns = ["CELL_" + str(c) for c in scRNA_data.columns]
     scRNA_data.index = ["GENE_" + str(g) for g in scRNA_data.index]
     scRNA_data = scRNA_data[~scRNA_data.index.duplicated(keep=False)]
@@ -766,15 +769,15 @@ def main_cytospace(scRNA_path, cell_type_path,
         with open(fout_log, "a") as f:
             f.write(line)
 
+    device = visible_devices(devices)[0]
     print("Read and validate data ...")
     t0 = time.perf_counter()
     scRNA_data, cell_type_data, st_data, coordinates_data, cell_type_fractions_data, n_cells_per_spot_data, st_cell_type_data = \
         read_data(scRNA_path, cell_type_path, cell_type_fraction_estimation_path, n_cells_per_spot_path, st_cell_type_path,
-                  output_path, output_prefix, spaceranger_path, st_path, coordinates_path)
+                  output_path, output_prefix, spaceranger_path, st_path, coordinates_path, device_id=device)
     all_spot_ids = st_data.columns
     print(f"Time to read and validate data: {round(time.perf_counter() - t0, 2)} seconds")
     log(f"Time to read and validate data: {round(time.perf_counter() - t0, 2)} seconds\n")
-    device = visible_devices(devices)[0]
 
     np.random.seed(seed)
     random.seed(seed)

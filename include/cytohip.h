@@ -26,7 +26,7 @@ enum {
     CYTO_ERR_INTERNAL = 4,      /* solver invariant violated */
     CYTO_ERR_HIP = 5,           /* a HIP runtime call failed; cyto_last_hip_error() has the text */
     CYTO_ERR_NO_DEVICE = 6,     /* no gfx950 device visible */
-    CYTO_ERR_UNSUPPORTED = 7,   /* size outside what this build supports (n > 262144 per LAP) */
+    CYTO_ERR_UNSUPPORTED = 7,   /* size outside what this build supports (n > 262144 per LAP); cyto_table_read: a file outside the grammar */
     CYTO_ERR_SHAPE = 8,         /* gene counts differ; reference: ValueError, common/common.py:191-192 */
     CYTO_ERR_PEER = 9           /* another rank of the communicator failed, aborted or did not arrive; reference: BrokenProcessPool */
 };
@@ -421,6 +421,35 @@ int cyto_downsample(int G, int C, const void *x, int64_t ldx, int x_dtype, void 
                     uint32_t *key, int32_t *pos, int64_t *words_out, int device_id);
 /* The generator alone (a test hook): the next n raw 32-bit MT19937 words from (key, *pos), with the state after them. */
 int cyto_mt19937_fill(uint32_t *key, int32_t *pos, int n, uint32_t *words, int device_id);
+
+/* ---- dense delimited text tables (cytospace_amd.common.read_file_device): pd.read_csv(path, sep, header=0, index_col=0) on the
+ * device.  The caller parses the header line; the data lines start at byte data_offset and each holds a row label and ncols values
+ * (sep ',' or '\t').  On success *out is a handle and shape = {G data lines, C = ncols, bytes of the packed labels}.
+ * CYTO_ERR_UNSUPPORTED: the file is outside the grammar and nothing is returned but reason = {CYTO_TABLE_ERR_*,
+ * the file's line (1-based, the header is line 1; 0 if none), the byte offset (the column for CYTO_TABLE_ERR_INT_CAST)}.
+ * ms (may be NULL): {host file reads, what the upload added to them, kernels and the small copies between them}. */
+typedef struct cyto_table cyto_table;
+enum {
+    CYTO_TABLE_ERR_IO = 1,        /* not a readable regular file, or it shrank while read */
+    CYTO_TABLE_ERR_BYTE = 2,      /* a control byte other than the delimiter, '\r', '\n' */
+    CYTO_TABLE_ERR_QUOTE = 3,     /* '"' in a data line */
+    CYTO_TABLE_ERR_CR = 4,        /* '\r' not followed by '\n' */
+    CYTO_TABLE_ERR_BLANK = 5,     /* an empty data line, or none at all */
+    CYTO_TABLE_ERR_FIELDS = 6,    /* a data line without exactly ncols delimiters */
+    CYTO_TABLE_ERR_TOKEN = 7,     /* a value outside the integer / decimal token grammar (NA, empty, text, 19+ digits) */
+    CYTO_TABLE_ERR_RANGE = 8,     /* a decimal token whose value is +-inf or whose decimal exponent exceeds 308 */
+    CYTO_TABLE_ERR_INT_CAST = 9   /* a float64 column with an integer token of 17 or 18 digits or a negative zero ("-0"): pandas'
+                                     block-wise int64 cast of it may differ from the decimal converter */
+};
+int cyto_table_read(const char *path, char sep, int64_t data_offset, int64_t ncols, int device_id, cyto_table **out, int64_t *shape,
+                    int64_t *reason, double *ms);
+/* values: G x C int64 words, row-major (a float64 column's words are its values' bits); col_is_float: C flags; labels: the row
+ * labels, each followed by sep and '\n' (shape[2] bytes); *ms_download (may be NULL). */
+int cyto_table_fetch(cyto_table *t, int64_t *values, int8_t *col_is_float, char *labels, double *ms_download);
+void cyto_table_free(cyto_table *t);
+/* The converter alone, on the host (a test hook): token i is text[offsets[i], offsets[i+1]); kinds[i] 0 integer token (ints[i],
+ * and values[i] as a decimal), 1 decimal token (values[i]), 2 outside the token grammar, 3 out of range. */
+int cyto_table_parse_tokens(const char *text, int64_t n, const int64_t *offsets, double *values, int64_t *ints, int8_t *kinds);
 
 #ifdef __cplusplus
 }
