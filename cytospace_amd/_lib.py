@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("CYTOHIP_LIB") or os.path.join(_HERE, "libcytohip.so")
 _lib = None
 
 CYTO_OK = 0
+CYTO_ERR_NONFINITE = 2   # NaN / Inf in a cost matrix (raised as ValueError)
 _EXC = {1: ValueError, 2: ValueError, 3: MemoryError, 7: ValueError, 8: ValueError}
 CYTO_ERR_PEER = 9        # another rank of the communicator failed (raised as CytoHipError)
 

@@ -136,15 +136,38 @@ def lap_repair_sparse(rowsol, row_ptr, cols, r):
     return out
 
 
-def lap_solve_batch(costs, device_id=0, max_concurrent=0, return_info=False, opts=None):
+def _batch_results(st, status, outs, totals, infos, return_info, return_status):
+    """The tail of the two batch calls.  return_status: a problem whose costs were rejected (CYTO_ERR_NONFINITE, the one status
+    that belongs to a problem and not to the call) does not raise; its slot is None and the statuses come back beside the results.
+    Every other non-zero status (bad arguments or options, HIP, memory, a solver invariant) raises as without return_status."""
+    stats = [int(x) for x in status]
+    if return_status:
+        for x in stats:
+            if x not in (_lib.CYTO_OK, _lib.CYTO_ERR_NONFINITE):
+                _lib.check(x)
+        if st not in (_lib.CYTO_OK, _lib.CYTO_ERR_NONFINITE):
+            _lib.check(st)
+    else:
+        _lib.check(st)
+    for b, o in enumerate(outs):
+        o["total"] = totals[b]
+        if return_info:
+            o["info"] = infos[b]
+    if return_status:
+        return [o if x == _lib.CYTO_OK else None for o, x in zip(outs, stats)], stats
+    return outs
+
+
+def lap_solve_batch(costs, device_id=0, max_concurrent=0, return_info=False, opts=None, return_status=False):
     """Solve several independent square LAPs concurrently on one GPU (C ABI: cyto_lap_batch_f32[_opts]).
 
     costs: list of 2-D float arrays (host).  opts: None or a dict of cyto_lap_opts fields for the whole batch.
-    Returns a list of dicts like lap_solve()."""
+    Returns a list of dicts like lap_solve().  return_status=True: (that list, [status per problem]) -- a problem with
+    non-finite costs is None in the list and CYTO_ERR_NONFINITE in the statuses instead of an exception for the call."""
     L = _lib.lib()
     nb = len(costs)
     if nb == 0:
-        return []
+        return ([], []) if return_status else []
     mats = [np.ascontiguousarray(c, dtype=np.float32) for c in costs]
     for c in mats:
         if c.ndim != 2 or c.shape[0] != c.shape[1] or c.shape[0] == 0:
@@ -164,20 +187,16 @@ def lap_solve_batch(costs, device_id=0, max_concurrent=0, return_info=False, opt
     o = _lib.LapOpts(**opts) if opts else None
     st = L.cyto_lap_batch_f32_opts(nb, ns, cptr, lds, 0, ptrs("rowsol"), ptrs("colsol"), ptrs("u"), ptrs("v"), totals, infos,
                                    status, max_concurrent, device_id, ctypes.byref(o) if o is not None else None)
-    _lib.check(st)
-    for b, o in enumerate(outs):
-        o["total"] = totals[b]
-        if return_info:
-            o["info"] = infos[b]
-    return outs
+    return _batch_results(st, status, outs, totals, infos, return_info, return_status)
 
 
-def lap_solve_batch_device(device_ptrs, ns, lds=None, device_id=0, max_concurrent=0, return_info=False, opts=None):
+def lap_solve_batch_device(device_ptrs, ns, lds=None, device_id=0, max_concurrent=0, return_info=False, opts=None,
+                           return_status=False):
     """lap_solve_batch for cost matrices that are already resident in HBM (row-major float32, ld elements per row)."""
     L = _lib.lib()
     nb = len(device_ptrs)
     if nb == 0:
-        return []
+        return ([], []) if return_status else []
     lds = list(ns) if lds is None else list(lds)
     n_arr = (ctypes.c_int * nb)(*[int(x) for x in ns])
     ld_arr = (ctypes.c_int64 * nb)(*[int(x) for x in lds])
@@ -194,9 +213,4 @@ def lap_solve_batch_device(device_ptrs, ns, lds=None, device_id=0, max_concurren
     o = _lib.LapOpts(**opts) if opts else None
     st = L.cyto_lap_batch_f32_opts(nb, n_arr, cptr, ld_arr, 1, ptrs("rowsol"), ptrs("colsol"), ptrs("u"), ptrs("v"), totals, infos,
                                    status, max_concurrent, device_id, ctypes.byref(o) if o is not None else None)
-    _lib.check(st)
-    for b, o in enumerate(outs):
-        o["total"] = totals[b]
-        if return_info:
-            o["info"] = infos[b]
-    return outs
+    return _batch_results(st, status, outs, totals, infos, return_info, return_status)

@@ -252,3 +252,44 @@ def test_read_file_matrix_market_and_tables(tmp_path):
         assert np.array_equal(back.to_numpy(), m.toarray()) and list(back.index) == list(t.index)
     with pytest.raises(IOError):
         read_file(str(tmp_path / "missing" / "matrix.mtx"))
+
+
+def test_batch_return_status_without_a_device(monkeypatch):
+    # lap_solve_batch(..., return_status=True): a problem with non-finite costs is a status and a None, not an exception for the
+    # call; every other status still raises.  The batch entry point is replaced by a stand-in that writes statuses (no device).
+    from cytospace_amd import _lib
+    from cytospace_amd.lap import lap_solve_batch, lap_solve_batch_device
+    real = _lib.lib()
+    plan = {}
+
+    class StandIn:
+        def __getattr__(self, name):
+            return getattr(real, name)
+
+        def cyto_lap_batch_f32_opts(self, nb, ns, cost, lds, on_device, rowsol, colsol, u, v, totals, infos, status, conc, dev, opts):
+            first = 0
+            for b in range(nb):
+                status[b] = plan["status"][b]
+                totals[b] = 10.0 + b
+                first = first or status[b]
+            return first
+
+    monkeypatch.setattr(_lib, "lib", lambda: StandIn())
+    costs = [np.zeros((3, 3), np.float32) for _ in range(4)]
+    plan["status"] = [0, 2, 0, 2]
+    with pytest.raises(ValueError):
+        lap_solve_batch(costs)                                         # the default: the first status raises
+    outs, status = lap_solve_batch(costs, return_status=True, return_info=True)
+    assert status == [0, 2, 0, 2] and outs[1] is None and outs[3] is None
+    assert outs[0]["total"] == 10.0 and outs[2]["total"] == 12.0 and "info" in outs[2] and outs[0]["colsol"].shape == (3,)
+    outs, status = lap_solve_batch_device([16, 32], [3, 3], return_status=True)
+    assert status == [0, 2] and outs[1] is None and outs[0]["total"] == 10.0
+    plan["status"] = [0, 0, 0, 0]
+    outs, status = lap_solve_batch(costs, return_status=True)
+    assert status == [0, 0, 0, 0] and all(o is not None for o in outs)
+    assert [o["total"] for o in lap_solve_batch(costs)] == [10.0, 11.0, 12.0, 13.0]
+    for code, exc in ((1, ValueError), (3, MemoryError), (4, _lib.CytoHipError), (5, _lib.CytoHipError)):
+        plan["status"] = [0, 2, code, 0]                                  # not a problem's own status: raises either way
+        with pytest.raises(exc):
+            lap_solve_batch(costs, return_status=True)
+    assert lap_solve_batch([]) == [] and lap_solve_batch([], return_status=True) == ([], [])

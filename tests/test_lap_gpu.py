@@ -154,7 +154,7 @@ def test_golden_known_answers(n):
 
 def test_batch_of_independent_laps():
     from cytospace_amd.lap import lap_solve_batch
-    sizes = [5, 300, 1200, 64, 2100, 700, 33]
+    sizes = [5, 300, 1200, 64, 2100, 700, 33]        # (all distinct: groups of ONE problem -- same-size groups, sub-batches and slices live in test_lap_batch_gpu.py)
     costs = [np.random.default_rng(100 + n).random((n, n)).astype(np.float32) for n in sizes]
     # a batch runs a workgroup per problem through one solver: the wide one by default, the chain solver on request
     for opts, oracle in ((None, jv_oracle_wide), (CHAIN, jv_oracle)):
