@@ -110,11 +110,23 @@ _NOT_TEXT = r"\s*[+-]?(?:(?:\d+\.?\d*|\.\d+)(?:[eE][+-]?\d+)?|inf|infinity|nan)\
 _CAST_LABEL = r"\s*[+-]?\d{17,}\s*|\s*-0+\s*"
 
 
+def _table_head(header, first, sep, C):
+    """pandas' parse of the header line with the first data line (it decides between the two header shapes): a frame of one row
+    whose columns and index name are the table's; None if pandas refuses it or does not see C data columns."""
+    import io
+    import pandas as pd
+    try:
+        head = pd.read_csv(io.BytesIO(header + first), sep=sep, header=0, index_col=0)
+    except Exception:
+        return None
+    if head.shape[1] != C or isinstance(head.index, pd.MultiIndex):
+        return None
+    return head
+
+
 def _table_on_device(file_path, device_id, info):
     """read_file_device's device path: the DataFrame, or None (info["reason"] says why) for a file outside its grammar."""
-    import io
     import time
-    import pandas as pd
 
     def refuse(kind, line=0, byte=0):
         info["reason"] = {"kind": kind, "line": int(line), "byte": int(byte)}
@@ -141,11 +153,8 @@ def _table_on_device(file_path, device_id, info):
     if C == 0:
         return refuse("no data columns", 2)
     t = time.perf_counter()
-    try:                                    # the header with the first data line: pandas decides between the two header shapes
-        head = pd.read_csv(io.BytesIO(header + first), sep=sep, header=0, index_col=0)
-    except Exception:
-        return refuse("header", 1)
-    if head.shape[1] != C or isinstance(head.index, pd.MultiIndex):
+    head = _table_head(header, first, sep, C)
+    if head is None:
         return refuse("header", 1)
     info["header_s"] = time.perf_counter() - t
     L = _lib.lib()
@@ -171,6 +180,19 @@ def _table_on_device(file_path, device_id, info):
         L.cyto_table_free(h)
         info["free_s"] = time.perf_counter() - t
     info["download_s"] = ms_dl.value / 1e3
+    return _table_frame(head, values, is_float, labels, sep, info)
+
+
+def _table_frame(head, values, is_float, labels, sep, info):
+    """The DataFrame of _table_on_device from what cyto_table_fetch gave (values: G x C int64 words, is_float: C flags, labels:
+    the packed row labels) and pandas' parse of the header; or None (info["reason"]) when the row labels are outside the grammar."""
+    import io
+    import time
+    import pandas as pd
+
+    def refuse(kind, line=0, byte=0):
+        info["reason"] = {"kind": kind, "line": int(line), "byte": int(byte)}
+        return None
     t = time.perf_counter()
     # the row labels, handed back to pandas as a table of their own: its inference (integers, NA, ...), duplicates kept
     index = pd.read_csv(io.BytesIO(labels.tobytes()), sep=sep, header=None, index_col=0).index
@@ -197,8 +219,8 @@ def read_file_device(file_path, device_id=0, return_info=False):
     """read_file(file_path, keep_sparse=False) for a dense delimited text table (.csv: ','; otherwise tab), parsed on the GPU
     (C ABI: cyto_table_read / cyto_table_fetch; csrc/table.hip).  The result is equal to read_file's: index, columns (pandas'
     header parse, duplicates mangled), every column's dtype (int64 or float64) and every value bit for bit (pandas' own decimal
-    converter).  A file outside the grammar of DESIGN.md 4.1c -- quotes, NA or empty values, ragged or blank lines, integers of 19+
-    digits, values beyond float64, MatrixMarket, compressed files, no data columns -- is read by read_file itself: its result, or
+    converter).  A file outside the grammar of DESIGN.md 4.1c -- quotes, NA or empty values, ragged or blank lines, numbers with 19+
+    digits before the point, values beyond float64, MatrixMarket, compressed files, no data columns -- is read by read_file itself: its result, or
     its exception.
 
     return_info: also return a dict -- "path" ("device" or "pandas"), for a fallback "reason" {"kind", "line", "byte"}, and the

@@ -59,8 +59,10 @@ enum { TOK_INT = 0, TOK_DEC = 1, TOK_BAD = 2, TOK_RANGE = 3 };
 __host__ __device__ inline bool is_digit(uint8_t c) { return c >= '0' && c <= '9'; }
 
 // One token [p, e): TOK_INT ([+-]?[0-9]{1,18}: *iv, and *d as the converter gives it), TOK_DEC (*d), TOK_BAD (outside the token
-// grammar, a digit string longer than 18 included: pandas makes it int64 or uint64) or TOK_RANGE (±inf, or a final decimal
-// exponent above 308: pandas leaves the column as text).  *nint: the digits before the point.
+// grammar) or TOK_RANGE (±inf, or a final decimal exponent above 308: pandas leaves the column as text).  *nint: the digits before
+// the point.  More than 18 of them are outside the grammar in an integer token (pandas makes it int64 or uint64) and in a decimal
+// token alike: pandas tries every column as int64 and then uint64 first, and where that attempt meets digits beyond uint64 before
+// it meets a token with a point or an exponent -- "7" above "56963997270084518163.5" -- it leaves the column as text.
 //
 // The decimal value is pandas' default converter, not a correctly rounded one: the first 17 digits (leading zeros count) are
 // accumulated in a double, later integer digits raise the exponent and later fraction digits are dropped; then one multiplication
@@ -117,7 +119,7 @@ __host__ __device__ inline int parse_token(const uint8_t *p, const uint8_t *e, d
     }
     if (p != e) return TOK_BAD;
     const bool integer = !dot && !has_e;
-    if (integer && nint > 18) return TOK_BAD;
+    if (nint > 18) return TOK_BAD;
     *nint_out = nint;
     if (integer) *iv = neg ? -(int64_t)acc : (int64_t)acc;
     exp -= ndec;

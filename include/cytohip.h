@@ -427,6 +427,12 @@ int cyto_mt19937_fill(uint32_t *key, int32_t *pos, int n, uint32_t *words, int d
  * (sep ',' or '\t').  On success *out is a handle and shape = {G data lines, C = ncols, bytes of the packed labels}.
  * CYTO_ERR_UNSUPPORTED: the file is outside the grammar and nothing is returned but reason = {CYTO_TABLE_ERR_*,
  * the file's line (1-based, the header is line 1; 0 if none), the byte offset (the column for CYTO_TABLE_ERR_INT_CAST)}.
+ * Which refusal a file with several gets: (1) data_offset at or beyond the file's end: {BLANK, 2, the file's size}; (2) else the
+ * lowest byte of the data region holding a '"' (QUOTE), a '\r' not followed by '\n' inside the file (CR) or a control byte
+ * (BYTE), wherever the defects below are; (3) else the lowest (byte, kind) among an empty line, a line of one '\r' included
+ * (BLANK, the line's first byte), a line without exactly ncols delimiters (FIELDS, the line's first byte) and, among the first
+ * ncols values of a line only, a value outside the grammar (TOKEN) or out of range (RANGE), at its first byte; (4) else the lowest
+ * column with both a decimal token and a "-0" or 17/18-digit integer token: {INT_CAST, 0, the column}.
  * ms (may be NULL): {host file reads, what the upload added to them, kernels and the small copies between them}. */
 typedef struct cyto_table cyto_table;
 enum {
@@ -436,7 +442,7 @@ enum {
     CYTO_TABLE_ERR_CR = 4,        /* '\r' not followed by '\n' */
     CYTO_TABLE_ERR_BLANK = 5,     /* an empty data line, or none at all */
     CYTO_TABLE_ERR_FIELDS = 6,    /* a data line without exactly ncols delimiters */
-    CYTO_TABLE_ERR_TOKEN = 7,     /* a value outside the integer / decimal token grammar (NA, empty, text, 19+ digits) */
+    CYTO_TABLE_ERR_TOKEN = 7,     /* a value outside the integer / decimal token grammar (NA, empty, text, 19+ digits before the point) */
     CYTO_TABLE_ERR_RANGE = 8,     /* a decimal token whose value is +-inf or whose decimal exponent exceeds 308 */
     CYTO_TABLE_ERR_INT_CAST = 9   /* a float64 column with an integer token of 17 or 18 digits or a negative zero ("-0"): pandas'
                                      block-wise int64 cast of it may differ from the decimal converter */

@@ -1,46 +1,12 @@
 """The device table reader's decimal converter (csrc/table.hip: parse_token, run on the host through cyto_table_parse_tokens)
-against pandas' own: 10^6 random tokens read by pd.read_csv as float64, compared bit for bit, and the integer tokens as int64."""
+against pandas' own: 10^6 random tokens read by pd.read_csv as float64, compared bit for bit, and the integer tokens as int64;
+and the tokens that are numbers but outside the grammar."""
 import io
 
 import numpy as np
 import pandas as pd
 
-
-def _tokens(n, seed=0):
-    rng = np.random.default_rng(seed)
-    out = []
-    digits = rng.integers(0, 10, (n, 24)).astype(str)
-    for i in range(n):
-        form = i % 6
-        nd = int(rng.integers(1, 25))
-        ds = "".join(digits[i, :nd])
-        if form == 0:                                   # 1-24 digits, a point somewhere, an exponent -300..280
-            p = int(rng.integers(0, nd + 1))
-            t = ds[:p] + "." + ds[p:] if rng.random() < 0.8 else ds
-            if rng.random() < 0.7:
-                t += f"{'eE'[i & 1]}{int(rng.integers(-300, 281)):+d}"
-        elif form == 1:                                 # long zero runs after the point
-            t = "0." + "0" * int(rng.integers(0, 40)) + ds[:int(rng.integers(1, 12))]
-        elif form == 2:                                 # 17-24 digit mantissas
-            t = "".join(digits[i, :int(rng.integers(17, 25))]).lstrip("0") or "0"
-            t = t + "." + ds[:3] if rng.random() < 0.5 else t + "e" + str(int(rng.integers(-20, 20)))
-        elif form == 3:                                 # below 1e-308: the two-step division, and below 1e-616
-            t = ds[:int(rng.integers(1, 18))] + "e" + str(int(rng.integers(-340, -300)) if rng.random() < 0.9 else -700)
-        elif form == 4:                                 # integer tokens of 1-18 digits
-            t = ds[:int(rng.integers(1, 19))]
-        else:                                           # short decimals, as written by R or to_csv
-            t = f"{rng.normal() * 10 ** int(rng.integers(-6, 7)):.{int(rng.integers(0, 9))}f}"
-        if rng.random() < 0.3 and not t.startswith("-"):
-            t = ("-" if rng.random() < 0.7 else "+") + t
-        if len(t.lstrip("+-")) > 18 and t.lstrip("+-").isdigit():
-            t += "."                                    # (a digit string of 19+ digits is no decimal token: pandas reads it as an integer)
-        out.append(t)
-    return out
-
-
-SPECIAL = ["-0", "-0.0", "5.", ".5", "007", "0", "+0", "0.0", "-.5", "999999999999999999", "-999999999999999999",
-           "000000000000000012", "0.000000000000000000000000001", "1.7976931348623157e308", "4.9e-324", "2.2250738585072011e-308",
-           "123456789012345678901234.", "-1e-700", "1e-330", "9.999999999999999999e-309"]
+from tools.table_cases import SPECIAL, in_grammar, random_tokens as _tokens     # (shared with the table files of the model tests)
 
 
 def _pandas_floats(tokens):
@@ -49,8 +15,12 @@ def _pandas_floats(tokens):
 
 def test_converter_equals_pandas_on_a_million_tokens():
     from cytospace_amd.common import parse_table_tokens
-    toks = SPECIAL + _tokens(1_000_000)
+    toks = SPECIAL + _tokens(1_200_000)
     kind, value, ints = parse_table_tokens(toks)
+    inside = np.array([in_grammar(t) for t in toks])     # (more than 18 digits before the point: see the test below)
+    assert (kind[~inside] == 2).all() and (~inside).sum() > 100_000
+    toks, kind, value, ints = [t for t, k in zip(toks, inside) if k], kind[inside], value[inside], ints[inside]
+    assert len(toks) >= 1_000_000
     assert set(np.unique(kind)) <= {0, 1}, [t for t, k in zip(toks, kind) if k > 1][:5]
     want = _pandas_floats(toks)
     bad = np.flatnonzero(value.view(np.int64) != want.view(np.int64))
@@ -59,6 +29,20 @@ def test_converter_equals_pandas_on_a_million_tokens():
     assert isint.sum() > 100_000
     want_int = pd.read_csv(io.StringIO("\n".join(np.asarray(toks, dtype=object)[isint])), header=None, dtype=np.int64)[0].to_numpy()
     assert np.array_equal(ints[isint], want_int)
+
+
+def test_decimal_tokens_with_more_than_18_integer_digits_are_outside_the_grammar():
+    # pandas tries a column as int64, then uint64, before float64; digits beyond uint64 met before a token with a point or an
+    # exponent end that attempt with an overflow, and the column stays text.  So the order of a column's tokens decides its type,
+    # and the reader leaves every such token to pandas: 18 digits can overflow neither int64 nor uint64.
+    from cytospace_amd.common import parse_table_tokens
+    assert pd.read_csv(io.StringIO("a\n7\n56963997270084518163.5\n"))["a"].dtype == object
+    assert pd.read_csv(io.StringIO("a\n18446744073709551616e0\n0.5\n"))["a"].dtype == object
+    assert pd.read_csv(io.StringIO("a\n0.5\n56963997270084518163.5\n"))["a"].dtype == np.float64
+    assert pd.read_csv(io.StringIO("a\n7\n999999999999999999.5\n-999999999999999999e1\n"))["a"].dtype == np.float64
+    kind, _, _ = parse_table_tokens(["56963997270084518163.5", "18446744073709551616e0", "1234567890123456789.", "-1234567890123456789e-30",
+                                     "0000000000000000000.5", "999999999999999999.5", "-999999999999999999e1", "123456789012345678."])
+    assert list(kind) == [2, 2, 2, 2, 2, 1, 1, 1]
 
 
 def test_special_tokens():
