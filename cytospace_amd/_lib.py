@@ -16,6 +16,11 @@ CYTO_OK = 0
 CYTO_ERR_NONFINITE = 2   # NaN / Inf in a cost matrix (raised as ValueError)
 _EXC = {1: ValueError, 2: ValueError, 3: MemoryError, 7: ValueError, 8: ValueError}
 CYTO_ERR_PEER = 9        # another rank of the communicator failed (raised as CytoHipError)
+CYTO_ERR_UNSUPPORTED = 7
+# element types (include/cytohip.h: CYTO_DTYPE_*)
+CYTO_DTYPE_F32, CYTO_DTYPE_F64, CYTO_DTYPE_U16, CYTO_DTYPE_U8, CYTO_DTYPE_I32, CYTO_DTYPE_I64 = range(6)
+# cyto_mtx_info.reason with CYTO_ERR_UNSUPPORTED (include/cytohip.h: CYTO_MTX_ERR_*)
+CYTO_MTX_ERR_FRACTION, CYTO_MTX_ERR_NONFINITE, CYTO_MTX_ERR_MAGNITUDE, CYTO_MTX_ERR_SQUARE, CYTO_MTX_ERR_IO = range(2, 7)
 
 
 class CytoHipError(RuntimeError):
@@ -70,6 +75,13 @@ class AssignInfo(ctypes.Structure):
 class Matrix(ctypes.Structure):
     """cyto_matrix (include/cytohip.h): a dense genes x columns array on the host or on the device."""
     _fields_ = [("data", ctypes.c_void_p), ("ld", ctypes.c_int64), ("is_f64", ctypes.c_int32), ("on_device", ctypes.c_int32)]
+
+
+class MtxInfo(ctypes.Structure):
+    """cyto_mtx_info (include/cytohip.h)."""
+    _fields_ = [("nnz", ctypes.c_int64), ("bytes", ctypes.c_int64), ("blocks", ctypes.c_int64), ("field", ctypes.c_int32),
+                ("reason", ctypes.c_int32), ("ms_upload", ctypes.c_double), ("ms_kernels", ctypes.c_double),
+                ("ms_download", ctypes.c_double), ("ms_write", ctypes.c_double)]
 
 
 class Chunk(ctypes.Structure):
@@ -163,6 +175,10 @@ def lib():
         L.cyto_table_free.restype = None
         L.cyto_table_parse_tokens.argtypes = [vp, i64, vp, vp, vp, vp]
         L.cyto_table_parse_tokens.restype = ctypes.c_int
+        L.cyto_mtx_write.argtypes = [ctypes.c_char_p, i64, i64, vp, i64, i32, vp, i64, i64, i32, ctypes.POINTER(MtxInfo)]
+        L.cyto_mtx_write.restype = ctypes.c_int
+        L.cyto_mtx_format_entries.argtypes = [vp, vp, vp, i32, i64, vp, vp]
+        L.cyto_mtx_format_entries.restype = ctypes.c_int
         L.cyto_comm_unique_id.argtypes = [ctypes.c_char_p]
         L.cyto_comm_init.argtypes = [ctypes.c_char_p, i32, i32, i32, ctypes.POINTER(vp)]
         L.cyto_comm_init_local.argtypes = [i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(vp)]

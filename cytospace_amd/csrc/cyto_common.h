@@ -48,6 +48,38 @@ struct DevBuf {
     template <typename U> U *as() const { return reinterpret_cast<U *>(p); }
 };
 
+// Plain device allocation for buffers as large as a call's input or output (a count matrix, a file's text): straight from the
+// runtime and back to it, not through the block cache.
+struct Mem {
+    void *p = nullptr;
+    Mem() = default;
+    Mem(const Mem &) = delete;
+    Mem &operator=(const Mem &) = delete;
+    ~Mem() { if (p) (void)hipFree(p); }
+    int alloc(size_t bytes) {
+        hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
+        if (e != hipSuccess) {
+            p = nullptr;
+            set_hip_error(e, "hipMalloc (plain buffer)");
+            return e == hipErrorOutOfMemory ? CYTO_ERR_NOMEM : CYTO_ERR_HIP;
+        }
+        return CYTO_OK;
+    }
+    template <typename U> U *as() const { return reinterpret_cast<U *>(p); }
+};
+
+// Two pinned host buffers of a double-buffered transfer (the caller fills p[] with hipHostMalloc).
+struct Pinned {
+    void *p[2] = {nullptr, nullptr};
+    Pinned() = default;
+    Pinned(const Pinned &) = delete;
+    Pinned &operator=(const Pinned &) = delete;
+    ~Pinned() {
+        for (void *q : p)
+            if (q) (void)hipHostFree(q);
+    }
+};
+
 // RAII events (timing brackets of one call); destroyed on every return path.
 template <int N> struct Events {
     hipEvent_t e[N] = {};

@@ -220,21 +220,7 @@ __global__ __launch_bounds__(HIST_T) void ds_hist(const TIn *x, int64_t ldx, int
     }
 }
 
-// Plain device allocation (these buffers are as large as the count matrix; they do not go through the block cache).
-struct Mem {
-    void *p = nullptr;
-    ~Mem() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) {
-        hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
-        if (e != hipSuccess) {
-            p = nullptr;
-            set_hip_error(e, "hipMalloc (downsample)");
-            return e == hipErrorOutOfMemory ? CYTO_ERR_NOMEM : CYTO_ERR_HIP;
-        }
-        return CYTO_OK;
-    }
-    template <typename U> U *as() const { return reinterpret_cast<U *>(p); }
-};
+// (Mem, cyto_common.h: these buffers are as large as the count matrix and do not go through the block cache)
 
 size_t dtype_size(int code) {
     switch (code) {

@@ -1,0 +1,490 @@
+// mtx.hip -- the assigned-expression MatrixMarket file (post_processing.write_mtx_device) formatted on the device, byte for byte what
+// scipy.io.mmwrite(path, coo_matrix(X[:, cols])) writes, or refused (CYTO_ERR_UNSUPPORTED) so that the caller writes it with scipy.
+//
+// X is the G x N source matrix, cols the C source columns of the assigned cells.  The file is a header and one line
+// "<gene+1> <cell+1> <value>\n" per non-zero X[gene, cols[cell]], genes ascending, then cells ascending.
+//   mtx_count    (a workgroup per gene) walks the gene's cells a segment of 512 at a time: the non-zeros and the exact bytes of their
+//                lines per segment, the segment's offset within the gene's text, the gene's totals; and which values are outside the
+//                device grammar (a real value that is not an integer below 2^53 -- 2^24 for float32).
+//   mtx_scan     (one workgroup) turns the genes' byte counts into int64 offsets into the body, and sums the non-zeros.
+//   mtx_format   (a workgroup per gene and segment) computes the line lengths again, scans them, formats the lines into LDS at the
+//                position their bytes have within the 16-byte chunks of the output, and stores whole chunks with 16-byte stores;
+//                the partial first and last chunk go out byte by byte.
+// The body is formatted in blocks of whole genes that fit a bounded device buffer; block k is downloaded into one of two pinned
+// buffers while block k + 1 is formatted and block k - 1 is written to the file.
+// fmt_line is the one formatter: the count pass, the format pass and the host (cyto_mtx_format_entries) all call it.
+#include "cyto_common.h"
+
+#include <errno.h>
+#include <fcntl.h>
+#include <math.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <chrono>
+#include <vector>
+
+namespace {
+
+using namespace cyto;
+
+constexpr int WG = 256;
+constexpr int EPT = 2;                                   // consecutive cells per thread
+constexpr int SEG = WG * EPT;                            // cells per segment
+constexpr int MAX_VALUE = 21;                            // "-9.007199254740991E15"; an int64 takes at most 20
+constexpr int MAX_LINE = 10 + 1 + 10 + 1 + MAX_VALUE + 1;   // G and C are below 2^31: at most 10 digits each
+constexpr int STAGE = SEG * MAX_LINE + 16;               // a segment's text, shifted by up to 15 bytes
+constexpr int64_t DEFAULT_BLOCK = int64_t(32) << 20;
+
+__host__ __device__ inline int ndigits32(uint32_t v) {
+    return v < 10u ? 1 : v < 100u ? 2 : v < 1000u ? 3 : v < 10000u ? 4 : v < 100000u ? 5 : v < 1000000u ? 6 : v < 10000000u ? 7
+         : v < 100000000u ? 8 : v < 1000000000u ? 9 : 10;
+}
+
+__host__ __device__ inline int ndigits64(uint64_t v) {
+    if (v <= 0xffffffffull) return ndigits32((uint32_t)v);
+    int n = 10;
+    for (uint64_t p = 10000000000ull; n < 20 && v >= p; p *= 10) n++;   // (p wraps only after n has reached 20)
+    return n;
+}
+
+// o[0, nd) := the nd decimal digits of v (nd = ndigits64(v)); 32-bit arithmetic once what is left fits.
+__host__ __device__ inline void put_digits(uint8_t *o, uint64_t v, int nd) {
+    int i = nd;
+    while (v > 0xffffffffull) {
+        const uint64_t q = v / 1000000000ull;
+        uint32_t r = (uint32_t)(v - q * 1000000000ull);
+        for (int k = 0; k < 9; k++) {
+            o[--i] = (uint8_t)('0' + r % 10u);
+            r /= 10u;
+        }
+        v = q;
+    }
+    uint32_t w = (uint32_t)v;
+    while (i > 0) {
+        o[--i] = (uint8_t)('0' + w % 10u);
+        w /= 10u;
+    }
+}
+
+// A value as the formatter takes it.  status: 0 a non-zero inside the grammar, 1 a zero (not written), else CYTO_MTX_ERR_*.
+struct Val {
+    int status;
+    bool neg;
+    uint64_t mag;
+};
+
+template <typename T> __host__ __device__ inline Val classify_int(T v) {
+    const bool neg = v < 0;
+    const uint64_t m = neg ? (uint64_t)0 - (uint64_t)(int64_t)v : (uint64_t)v;
+    return Val{m == 0 ? 1 : 0, neg, m};
+}
+__host__ __device__ inline Val classify_real(double v, double limit) {
+    if (v == 0.0) return Val{1, false, 0};
+    const double a = fabs(v);
+    if (!(a <= 1.7976931348623157e308)) return Val{CYTO_MTX_ERR_NONFINITE, false, 0};
+    if (a >= limit) return Val{CYTO_MTX_ERR_MAGNITUDE, false, 0};
+    if (a != floor(a)) return Val{CYTO_MTX_ERR_FRACTION, false, 0};
+    return Val{0, v < 0.0, (uint64_t)a};
+}
+__host__ __device__ inline Val classify(uint8_t v) { return classify_int(v); }
+__host__ __device__ inline Val classify(uint16_t v) { return classify_int(v); }
+__host__ __device__ inline Val classify(int32_t v) { return classify_int(v); }
+__host__ __device__ inline Val classify(int64_t v) { return classify_int(v); }
+// scipy writes the shortest digits that read back as the same value OF THE SOURCE TYPE: they are the integer's own digits while
+// the type's spacing is at most 1, that is below 2^24 for float32 and below 2^53 for float64.
+__host__ __device__ inline Val classify(float v) { return classify_real((double)v, 16777216.0); }
+__host__ __device__ inline Val classify(double v) { return classify_real(v, 9007199254740992.0); }
+template <typename T> struct is_real { static constexpr bool value = false; };
+template <> struct is_real<float> { static constexpr bool value = true; };
+template <> struct is_real<double> { static constexpr bool value = true; };
+
+// The value's text; returns its length.  WRITE = false: the length alone (o is not touched).
+// integer field: plain decimal.  real field: the digits of m without trailing zeros, a '.' after the first when more than one is
+// left, and "E<k>", k = the digit count of m minus 1, when k > 0.
+template <bool WRITE> __host__ __device__ inline int fmt_value(uint8_t *o, bool real, bool neg, uint64_t m) {
+    int n = 0;
+    if (neg) {
+        if (WRITE) o[n] = '-';
+        n++;
+    }
+    const int nd = ndigits64(m);
+    if (!real) {
+        if (WRITE) put_digits(o + n, m, nd);
+        return n + nd;
+    }
+    int sig = nd;
+    if (m <= 0xffffffffull) {
+        uint32_t s = (uint32_t)m;
+        while (s % 10u == 0) s /= 10u, sig--;
+        m = s;
+    } else {
+        while (m % 10u == 0) m /= 10u, sig--;
+    }
+    if (sig == 1) {
+        if (WRITE) o[n] = (uint8_t)('0' + m);
+        n++;
+    } else {
+        if (WRITE) {
+            put_digits(o + n + 1, m, sig);
+            o[n] = o[n + 1];
+            o[n + 1] = '.';
+        }
+        n += sig + 1;
+    }
+    int k = nd - 1;                                      // at most 15
+    if (k > 0) {
+        if (WRITE) o[n] = 'E';
+        n++;
+        if (k >= 10) {
+            if (WRITE) o[n] = '1';
+            n++;
+            k -= 10;
+        }
+        if (WRITE) o[n] = (uint8_t)('0' + k);
+        n++;
+    }
+    return n;
+}
+
+// "<row1> <col1> <value>\n"; returns its length.
+template <bool WRITE> __host__ __device__ inline int fmt_line(uint8_t *o, uint64_t row1, uint64_t col1, bool real, const Val &v) {
+    const int nr = ndigits64(row1), nc = ndigits64(col1);
+    if (WRITE) {
+        put_digits(o, row1, nr);
+        o[nr] = ' ';
+        put_digits(o + nr + 1, col1, nc);
+        o[nr + 1 + nc] = ' ';
+    }
+    int n = nr + nc + 2;
+    n += fmt_value<WRITE>(o + n, real, v.neg, v.mag);
+    if (WRITE) o[n] = '\n';
+    return n + 1;
+}
+
+// Exclusive scan of one value per thread across the workgroup; *total: the sum.  Every thread must call it.
+template <typename V> __device__ __forceinline__ V wg_scan(V v, V *total) {
+    __shared__ V wsum[WG / 64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    V x = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const V y = __shfl_up(x, off, 64);
+        if (lane >= off) x += y;
+    }
+    if (lane == 63) wsum[w] = x;
+    __syncthreads();
+    V before = 0, tot = 0;
+#pragma unroll
+    for (int i = 0; i < WG / 64; i++) {
+        before += i < w ? wsum[i] : V(0);
+        tot += wsum[i];
+    }
+    __syncthreads();                                    // (wsum is reused by the next call)
+    *total = tot;
+    return before + x - v;
+}
+
+// A workgroup per gene g.  seg_off[g * nseg + s] := the bytes of gene g's lines before segment s; row_bytes[g], row_nnz[g] := its
+// totals; *flags |= 1 << CYTO_MTX_ERR_* for every kind of value outside the grammar.
+template <typename T>
+__global__ __launch_bounds__(WG) void mtx_count(const T *X, int64_t ldx, const int64_t *cols, int64_t C, int nseg, int64_t *seg_off,
+                                                int64_t *row_bytes, int64_t *row_nnz, int *flags) {
+    const int64_t g = blockIdx.x;
+    const T *xr = X + g * ldx;
+    int64_t run = 0, nz = 0;
+    int bad = 0;
+    for (int s = 0; s < nseg; s++) {
+        int packed = 0;                                 // bytes (at most SEG * MAX_LINE < 2^16) | non-zeros << 16
+#pragma unroll
+        for (int k = 0; k < EPT; k++) {
+            const int64_t j = (int64_t)s * SEG + threadIdx.x * EPT + k;
+            if (j >= C) break;
+            const Val v = classify(xr[cols[j]]);
+            if (v.status == 0) packed += (1 << 16) + fmt_line<false>(nullptr, (uint64_t)g + 1, (uint64_t)j + 1, is_real<T>::value, v);
+            else if (v.status > 1) bad |= 1 << v.status;
+        }
+        int tot;
+        wg_scan(packed, &tot);
+        if (threadIdx.x == 0) seg_off[g * nseg + s] = run;
+        run += tot & 0xffff;
+        nz += tot >> 16;
+    }
+    if (threadIdx.x == 0) {
+        row_bytes[g] = run;
+        row_nnz[g] = nz;
+    }
+    if (bad) atomicOr(flags, bad);
+}
+
+// One workgroup: row_off[0 .. G] := exclusive prefix sum of row_bytes (row_off[G]: the body's bytes), *nnz := the sum of row_nnz.
+__global__ __launch_bounds__(WG) void mtx_scan(const int64_t *row_bytes, const int64_t *row_nnz, int64_t G, int64_t *row_off, int64_t *nnz) {
+    int64_t carry = 0, nz = 0;
+    for (int64_t g0 = 0; g0 < G; g0 += WG) {
+        const int64_t g = g0 + threadIdx.x;
+        int64_t tot, tnz;
+        const int64_t ex = wg_scan<int64_t>(g < G ? row_bytes[g] : 0, &tot);
+        wg_scan<int64_t>(g < G ? row_nnz[g] : 0, &tnz);
+        if (g < G) row_off[g] = carry + ex;
+        carry += tot;
+        nz += tnz;
+    }
+    if (threadIdx.x == 0) {
+        row_off[G] = carry;
+        *nnz = nz;
+    }
+}
+
+// Workgroup w of the launch: gene g0 + w / nseg, segment w % nseg.  out: the block's text, its first byte being byte `base` of the body
+// (out is 16-byte aligned).
+template <typename T>
+__global__ __launch_bounds__(WG) void mtx_format(const T *X, int64_t ldx, const int64_t *cols, int64_t C, int nseg, int64_t g0,
+                                                 const int64_t *row_off, const int64_t *seg_off, int64_t base, uint8_t *out) {
+    __shared__ uint4 stage4[(STAGE + 15) / 16];
+    uint8_t *stage = reinterpret_cast<uint8_t *>(stage4);
+    const int64_t g = g0 + blockIdx.x / nseg;
+    const int s = (int)(blockIdx.x % nseg);
+    const T *xr = X + g * ldx;
+    Val v[EPT];
+    int len[EPT], mine = 0;
+#pragma unroll
+    for (int k = 0; k < EPT; k++) {
+        const int64_t j = (int64_t)s * SEG + threadIdx.x * EPT + k;
+        len[k] = 0;
+        if (j < C) {
+            v[k] = classify(xr[cols[j]]);
+            if (v[k].status == 0) len[k] = fmt_line<false>(nullptr, (uint64_t)g + 1, (uint64_t)j + 1, is_real<T>::value, v[k]);
+        }
+        mine += len[k];
+    }
+    int tot;
+    const int ex = wg_scan(mine, &tot);
+    if (tot == 0) return;
+    const int64_t dst = row_off[g] - base + seg_off[g * nseg + s];
+    const int shift = (int)(dst & 15);                  // stage[p] is byte (dst - shift + p) of out: chunks line up
+    uint8_t *p = stage + shift + ex;
+#pragma unroll
+    for (int k = 0; k < EPT; k++)
+        if (len[k]) {
+            const int64_t j = (int64_t)s * SEG + threadIdx.x * EPT + k;
+            fmt_line<true>(p, (uint64_t)g + 1, (uint64_t)j + 1, is_real<T>::value, v[k]);
+            p += len[k];
+        }
+    __syncthreads();
+    uint8_t *o = out + (dst - shift);
+    const int span = shift + tot;
+    for (int c = threadIdx.x; c * 16 < span; c += WG) {
+        const int lo = c * 16, hi = lo + 16;
+        if (lo >= shift && hi <= span) {
+            *reinterpret_cast<uint4 *>(o + lo) = stage4[c];
+        } else {
+            for (int b = lo < shift ? shift : lo; b < (hi < span ? hi : span); b++) o[b] = stage[b];
+        }
+    }
+}
+
+// The output file: removed again unless the whole of it was written.
+struct OutFile {
+    int fd = -1;
+    const char *path = nullptr;
+    bool keep = false;
+    ~OutFile() {
+        if (fd < 0) return;
+        close(fd);
+        if (!keep) unlink(path);
+    }
+    bool write_all(const void *buf, size_t n) {
+        const char *q = static_cast<const char *>(buf);
+        while (n > 0) {
+            const ssize_t r = write(fd, q, n);
+            if (r < 0 && errno == EINTR) continue;
+            if (r <= 0) return false;
+            q += r;
+            n -= (size_t)r;
+        }
+        return true;
+    }
+};
+
+double ms_since(std::chrono::steady_clock::time_point t) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+}
+
+size_t dtype_size(int dt) {
+    switch (dt) {
+    case CYTO_DTYPE_U8: return 1;
+    case CYTO_DTYPE_U16: return 2;
+    case CYTO_DTYPE_F32: case CYTO_DTYPE_I32: return 4;
+    case CYTO_DTYPE_F64: case CYTO_DTYPE_I64: return 8;
+    }
+    return 0;
+}
+
+// CALL with T bound to the element type of CYTO_DTYPE_* dt
+#define MTX_DISPATCH(dt, CALL)                                     \
+    switch (dt) {                                                  \
+    case CYTO_DTYPE_F32: { using T = float; CALL; } break;         \
+    case CYTO_DTYPE_F64: { using T = double; CALL; } break;        \
+    case CYTO_DTYPE_U16: { using T = uint16_t; CALL; } break;      \
+    case CYTO_DTYPE_U8: { using T = uint8_t; CALL; } break;        \
+    case CYTO_DTYPE_I32: { using T = int32_t; CALL; } break;       \
+    default: { using T = int64_t; CALL; } break;                   \
+    }
+
+}  // namespace
+
+int cyto_mtx_write(const char *path, int64_t G, int64_t N, const void *x, int64_t ldx, int x_dtype, const int64_t *cols, int64_t C,
+                   int64_t block_bytes, int device_id, cyto_mtx_info *info) {
+    const size_t es = dtype_size(x_dtype);
+    if (!path || !x || !cols || !info || es == 0 || G <= 0 || N <= 0 || C <= 0 || ldx < N || block_bytes < 0 || G > 0x7fffffffll ||
+        C > 0x7fffffffll)
+        return CYTO_ERR_BAD_ARG;
+    for (int64_t j = 0; j < C; j++)
+        if (cols[j] < 0 || cols[j] >= N) return CYTO_ERR_BAD_ARG;
+    *info = cyto_mtx_info{};
+    const bool real = x_dtype == CYTO_DTYPE_F32 || x_dtype == CYTO_DTYPE_F64;
+    info->field = real ? 1 : 0;
+    auto refuse = [&](int kind) {                       // nothing stays at `path`, not even an earlier file
+        info->reason = kind;
+        unlink(path);
+        return (int)CYTO_ERR_UNSUPPORTED;
+    };
+    if (G == C) return refuse(CYTO_MTX_ERR_SQUARE);     // scipy looks for symmetry in a square matrix and may write a triangle
+    int rc;
+    if ((rc = select_device(device_id))) return rc;
+    const int nseg = (int)((C + SEG - 1) / SEG);
+    // (declared before the streams: they drain before any buffer or copy source / destination is freed, whatever path leaves the call)
+    Mem dx, dcols, seg_off, row_bytes, row_nnz, row_off, scal, dbuf[2];
+    Pinned pin;
+    Events<8> ev;                                       // per buffer b: format start / end (b, 2 + b), download start / end (4 + b, 6 + b)
+    std::vector<int64_t> hoff((size_t)G + 1);
+    int64_t hs[2] = {0, 0};
+    OutFile f;
+    StreamGuard sg, sc;
+    if ((rc = sg.acquire()) || (rc = sc.acquire()) || (rc = ev.create())) return rc;
+    if ((rc = dx.alloc((size_t)(G * ldx) * es)) || (rc = dcols.alloc((size_t)C * 8)) || (rc = seg_off.alloc((size_t)(G * nseg) * 8)) ||
+        (rc = row_bytes.alloc((size_t)G * 8)) || (rc = row_nnz.alloc((size_t)G * 8)) || (rc = row_off.alloc((size_t)(G + 1) * 8)) ||
+        (rc = scal.alloc(16)))
+        return rc;
+
+    // (1) the matrix and the column list
+    const auto t0 = std::chrono::steady_clock::now();
+    CYTO_HIP(hipMemcpyAsync(dx.p, x, (size_t)(G * ldx) * es, hipMemcpyHostToDevice, sg.s));
+    CYTO_HIP(hipMemcpyAsync(dcols.p, cols, (size_t)C * 8, hipMemcpyHostToDevice, sg.s));
+    CYTO_HIP(hipStreamSynchronize(sg.s));
+    info->ms_upload = ms_since(t0);
+
+    // (2) counts, offsets, the values outside the grammar
+    const auto t1 = std::chrono::steady_clock::now();
+    CYTO_HIP(hipMemsetAsync(scal.p, 0, 16, sg.s));
+    MTX_DISPATCH(x_dtype, hipLaunchKernelGGL(mtx_count<T>, dim3((unsigned)G), dim3(WG), 0, sg.s, dx.as<T>(), ldx, dcols.as<int64_t>(), C,
+                                             nseg, seg_off.as<int64_t>(), row_bytes.as<int64_t>(), row_nnz.as<int64_t>(),
+                                             scal.as<int>() + 2));
+    CYTO_HIP(hipGetLastError());
+    hipLaunchKernelGGL(mtx_scan, dim3(1), dim3(WG), 0, sg.s, row_bytes.as<int64_t>(), row_nnz.as<int64_t>(), G, row_off.as<int64_t>(),
+                       scal.as<int64_t>());
+    CYTO_HIP(hipGetLastError());
+    CYTO_HIP(hipMemcpyAsync(hs, scal.p, 16, hipMemcpyDeviceToHost, sg.s));
+    CYTO_HIP(hipMemcpyAsync(hoff.data(), row_off.p, (size_t)(G + 1) * 8, hipMemcpyDeviceToHost, sg.s));
+    CYTO_HIP(hipStreamSynchronize(sg.s));
+    info->ms_kernels = ms_since(t1);
+    const int flags = (int)(hs[1] & 0xffffffff);
+    for (int kind : {CYTO_MTX_ERR_NONFINITE, CYTO_MTX_ERR_FRACTION, CYTO_MTX_ERR_MAGNITUDE})
+        if (flags & (1 << kind)) return refuse(kind);
+    const int64_t body = hoff[(size_t)G];
+    info->nnz = hs[0];
+
+    // (3) the header; the body in blocks of whole genes
+    char head[128];
+    if (hs[0] == 0) info->field = 1;                    // scipy names the field of a matrix without entries "real", whatever its type
+    const int nh = snprintf(head, sizeof head, "%%%%MatrixMarket matrix coordinate %s general\n%%\n%lld %lld %lld\n",
+                            info->field ? "real" : "integer", (long long)G, (long long)C, (long long)hs[0]);
+    info->bytes = nh + body;
+    f.path = path;
+    f.fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (f.fd < 0) return refuse(CYTO_MTX_ERR_IO);
+    auto io_failed = [&]() { return refuse(CYTO_MTX_ERR_IO); };
+    auto tw = std::chrono::steady_clock::now();
+    if (!f.write_all(head, (size_t)nh)) return io_failed();
+    info->ms_write = ms_since(tw);
+    if (body == 0) {
+        f.keep = true;
+        return CYTO_OK;
+    }
+    const int64_t cap = block_bytes ? block_bytes : DEFAULT_BLOCK;
+    std::vector<int64_t> first;                         // block k: genes [first[k], first[k + 1]); a gene larger than the cap stands alone
+    int64_t largest = 0;
+    for (int64_t g = 0; g < G;) {
+        int64_t e = g + 1;
+        while (e < G && hoff[(size_t)e + 1] - hoff[(size_t)g] <= cap) e++;
+        first.push_back(g);
+        largest = std::max(largest, hoff[(size_t)e] - hoff[(size_t)g]);
+        g = e;
+    }
+    first.push_back(G);
+    const int64_t nb = (int64_t)first.size() - 1;
+    info->blocks = nb;
+    const size_t bufsz = (size_t)largest + 16;
+    for (int b = 0; b < (nb > 1 ? 2 : 1); b++) {
+        if ((rc = dbuf[b].alloc(bufsz))) return rc;
+        CYTO_HIP(hipHostMalloc(&pin.p[b], bufsz, hipHostMallocDefault));
+    }
+    const int64_t max_rows = std::max<int64_t>(1, (int64_t(1) << 30) / nseg);      // workgroups of one launch
+    auto block_len = [&](int64_t k) { return hoff[(size_t)first[(size_t)k + 1]] - hoff[(size_t)first[(size_t)k]]; };
+    auto finish = [&](int64_t k) -> int {               // block k has been formatted and its download queued: wait, write
+        const int b = (int)(k & 1);
+        const int64_t n = block_len(k);
+        if (n == 0) return CYTO_OK;
+        CYTO_HIP(hipEventSynchronize(ev[6 + b]));
+        float ms = 0;
+        CYTO_HIP(hipEventElapsedTime(&ms, ev[b], ev[2 + b]));
+        info->ms_kernels += ms;
+        CYTO_HIP(hipEventElapsedTime(&ms, ev[4 + b], ev[6 + b]));
+        info->ms_download += ms;
+        tw = std::chrono::steady_clock::now();
+        if (!f.write_all(pin.p[b], (size_t)n)) return io_failed();
+        info->ms_write += ms_since(tw);
+        return CYTO_OK;
+    };
+    for (int64_t k = 0; k < nb; k++) {
+        const int b = (int)(k & 1);
+        const int64_t ga = first[(size_t)k], gb = first[(size_t)k + 1], n = block_len(k);
+        if (n > 0) {
+            CYTO_HIP(hipEventRecord(ev[b], sg.s));
+            for (int64_t r0 = ga; r0 < gb; r0 += max_rows) {
+                const int64_t rows = std::min(max_rows, gb - r0);
+                MTX_DISPATCH(x_dtype, hipLaunchKernelGGL(mtx_format<T>, dim3((unsigned)(rows * nseg)), dim3(WG), 0, sg.s, dx.as<T>(), ldx,
+                                                         dcols.as<int64_t>(), C, nseg, r0, row_off.as<int64_t>(), seg_off.as<int64_t>(),
+                                                         hoff[(size_t)ga], dbuf[b].as<uint8_t>()));
+                CYTO_HIP(hipGetLastError());
+            }
+            CYTO_HIP(hipEventRecord(ev[2 + b], sg.s));
+            CYTO_HIP(hipStreamWaitEvent(sc.s, ev[2 + b], 0));
+            CYTO_HIP(hipEventRecord(ev[4 + b], sc.s));
+            CYTO_HIP(hipMemcpyAsync(pin.p[b], dbuf[b].p, (size_t)n, hipMemcpyDeviceToHost, sc.s));
+            CYTO_HIP(hipEventRecord(ev[6 + b], sc.s));
+        }
+        if (k > 0 && (rc = finish(k - 1))) return rc;
+    }
+    if ((rc = finish(nb - 1))) return rc;
+    f.keep = true;
+    return CYTO_OK;
+}
+
+int cyto_mtx_format_entries(const int64_t *rows, const int64_t *cols, const void *values, int dtype, int64_t n, char *out,
+                            int64_t *offsets) {
+    if (n < 0 || !offsets || dtype_size(dtype) == 0 || (n > 0 && (!rows || !cols || !values || !out))) return CYTO_ERR_BAD_ARG;
+    uint8_t *o = reinterpret_cast<uint8_t *>(out);
+    int64_t at = 0;
+    offsets[0] = 0;
+    for (int64_t i = 0; i < n; i++) {
+        if (rows[i] < 0 || cols[i] < 0) return CYTO_ERR_BAD_ARG;
+        Val v{};
+        bool real = false;
+        MTX_DISPATCH(dtype, (v = classify(static_cast<const T *>(values)[i]), real = is_real<T>::value));
+        if (v.status > 1) return CYTO_ERR_UNSUPPORTED;
+        if (v.status == 0) at += fmt_line<true>(o + at, (uint64_t)rows[i] + 1, (uint64_t)cols[i] + 1, real, v);
+        offsets[i + 1] = at;
+    }
+    return CYTO_OK;
+}

@@ -313,32 +313,9 @@ __global__ __launch_bounds__(WG) void tbl_labels(const uint8_t *T, const int64_t
     o[n + 1] = '\n';
 }
 
-// Plain device allocation, as downsample.hip's: the text and the result are as large as the input and do not go through the
-// block cache.
-struct Mem {
-    void *p = nullptr;
-    ~Mem() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) {
-        hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
-        if (e != hipSuccess) {
-            p = nullptr;
-            set_hip_error(e, "hipMalloc (table)");
-            return e == hipErrorOutOfMemory ? CYTO_ERR_NOMEM : CYTO_ERR_HIP;
-        }
-        return CYTO_OK;
-    }
-    template <typename U> U *as() const { return reinterpret_cast<U *>(p); }
-};
-
-// Two pinned chunk buffers for the streamed upload.
+// (Mem, cyto_common.h: the text and the result are as large as the input and do not go through the block cache; Pinned: the two
+// chunk buffers of the streamed upload)
 constexpr size_t CHUNK = size_t(16) << 20;
-struct Pinned {
-    void *p[2] = {nullptr, nullptr};
-    ~Pinned() {
-        for (void *q : p)
-            if (q) (void)hipHostFree(q);
-    }
-};
 
 struct Fd {
     int fd = -1;

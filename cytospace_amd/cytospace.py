@@ -863,7 +863,7 @@ def main_cytospace(scRNA_path, cell_type_path,
               f"{output_path}/{output_prefix}unassigned_locations.csv")
     save_results(output_path, output_prefix, cell_ids_selected,
                  scRNA_data_sampled if sampling_method == "place_holders" else scRNA_data,
-                 assigned_locations, cell_type_data, sampling_method, single_cell)
+                 assigned_locations, cell_type_data, sampling_method, single_cell, device_id=device)
     if not plot_off:
         print("Plotting is not part of this package: no plots are produced (the results are written as files).")
     print(f"Total execution time: {round(time.perf_counter() - start_time, 2)} seconds")

@@ -1,7 +1,8 @@
 """Output writers of the reference: `save_results`
 (/root/reference/cytospace/post_processing/post_processing.py:10-116) and the unassigned-spot table written by
-main_cytospace (/root/reference/cytospace/cytospace.py:686-694).  Pure host code (pandas), same file names, columns and
-ordering, so a run of this package can be post-processed by the same downstream scripts.  Written from the format, not
+main_cytospace (/root/reference/cytospace/cytospace.py:686-694).  Host code (pandas), same file names, columns and
+ordering, so a run of this package can be post-processed by the same downstream scripts; with a device, the one large file
+(assigned_expression/matrix.mtx) is formatted on the GPU by write_mtx_device, byte for byte what scipy writes.  Written from the format, not
 from the reference's statements: tests/golden/gv12_* holds files the reference itself wrote for the same inputs.
 """
 import math
@@ -9,6 +10,8 @@ import os
 
 import numpy as np
 import pandas as pd
+
+from . import _lib
 
 
 def _strip(prefix, names):
@@ -35,9 +38,115 @@ def assigned_locations_table(cell_ids_selected, assigned_locations, cell_type_da
     return pd.DataFrame.from_dict(cols)
 
 
+# numpy dtype -> (the dtype uploaded, CYTO_DTYPE_*) of write_mtx_device; every other dtype is written by scipy
+_MTX_DTYPES = {"uint8": (np.uint8, _lib.CYTO_DTYPE_U8), "uint16": (np.uint16, _lib.CYTO_DTYPE_U16), "int8": (np.int32, _lib.CYTO_DTYPE_I32),
+               "int16": (np.int32, _lib.CYTO_DTYPE_I32), "int32": (np.int32, _lib.CYTO_DTYPE_I32), "int64": (np.int64, _lib.CYTO_DTYPE_I64),
+               "float32": (np.float32, _lib.CYTO_DTYPE_F32), "float64": (np.float64, _lib.CYTO_DTYPE_F64)}
+_MTX_REFUSALS = {_lib.CYTO_MTX_ERR_FRACTION: "non-integer value", _lib.CYTO_MTX_ERR_NONFINITE: "non-finite value",
+                 _lib.CYTO_MTX_ERR_MAGNITUDE: "magnitude", _lib.CYTO_MTX_ERR_SQUARE: "square", _lib.CYTO_MTX_ERR_IO: "io"}
+
+
+def _mtx_narrow(x):
+    """x (one of _MTX_DTYPES) as the narrowest array the device formats to the same text, and its CYTO_DTYPE_*.  Integers: the
+    field stays "integer" (uint8 / uint16 / int32 / int64 by range).  float64: float32 when every value is one and lies below 2^24,
+    where both types' shortest digits are the integer's own."""
+    to, code = _MTX_DTYPES[x.dtype.name]
+    if x.dtype.kind in "iu" and x.size:
+        lo, hi = int(x.min()), int(x.max())
+        if lo >= 0 and hi < (1 << 8):
+            to, code = np.uint8, _lib.CYTO_DTYPE_U8
+        elif lo >= 0 and hi < (1 << 16):
+            to, code = np.uint16, _lib.CYTO_DTYPE_U16
+        elif -(1 << 31) <= lo and hi < (1 << 31):
+            to, code = np.int32, _lib.CYTO_DTYPE_I32
+    elif x.dtype == np.float64 and x.size:
+        if -(1 << 24) < x.min() and x.max() < (1 << 24):     # (False with a NaN: the device refuses it whatever the type)
+            x32 = x.astype(np.float32)
+            step = max(1, (1 << 24) // x.shape[1])           # (compared in row blocks: array_equal widens its block to float64)
+            if all(np.array_equal(x32[r:r + step], x[r:r + step]) for r in range(0, x.shape[0], step)):
+                return np.ascontiguousarray(x32), _lib.CYTO_DTYPE_F32
+    return np.ascontiguousarray(x, dtype=to), code
+
+
+def write_mtx_device(path, matrix_or_frame, columns, device_id=0, block_bytes=0, return_info=False):
+    """scipy.io.mmwrite(path, scipy.sparse.coo_matrix(frame.iloc[:, columns])) with the text formatted on the GPU (C ABI:
+    cyto_mtx_write; csrc/mtx.hip): the same bytes.  matrix_or_frame: genes x cells, a DataFrame or a 2-D array; columns: the
+    positions (not labels) of the cells to write, in file order, repeats allowed.  block_bytes: the most text per device buffer
+    (0: the library's default; tests force many blocks with it).
+
+    What the device does not format is written by scipy itself: a real matrix with a non-zero that is not an
+    integer below 2^53 (2^24 for float32), a square result, a dtype other than int8..int64 / uint8 / uint16 / float32 / float64,
+    a frame whose column labels are not unique or whose selected columns have another common dtype than the whole frame, an empty
+    result, a path that is not a str.
+
+    return_info: also return a dict -- "path" ("device" or "scipy"), for a fallback "reason", and for the device "nnz", "bytes",
+    "field", "blocks" and the phase times in seconds: narrow_s (the host's choice of the upload dtype), library_s (the whole
+    cyto_mtx_write call: device and pinned allocations and their release besides the next four), upload_s, kernels_s, download_s
+    (overlaps the others), write_s, total_s."""
+    import ctypes
+    import time
+    import pandas as pd
+    import scipy.io
+    import scipy.sparse
+    t0 = time.perf_counter()
+    info = {"path": "device"}
+    frame = matrix_or_frame if isinstance(matrix_or_frame, pd.DataFrame) else None
+    if frame is None:
+        matrix_or_frame = np.asarray(matrix_or_frame)
+        if matrix_or_frame.ndim != 2:
+            raise ValueError("write_mtx_device needs a 2-D matrix")
+    G, N = matrix_or_frame.shape
+    columns = np.asarray(columns, dtype=np.int64).reshape(-1)
+    if columns.size and (columns.min() < -N or columns.max() >= N):
+        raise IndexError("positional indexers are out-of-bounds")
+    columns = np.ascontiguousarray(np.where(columns < 0, columns + N, columns))
+    C = len(columns)
+
+    def selected():
+        return frame.iloc[:, columns] if frame is not None else matrix_or_frame[:, columns]
+
+    def refuse(reason):
+        info.update(path="scipy", reason=reason)
+        scipy.io.mmwrite(path, scipy.sparse.coo_matrix(selected()))
+        info["total_s"] = time.perf_counter() - t0
+        return info if return_info else None
+
+    if not isinstance(path, str):
+        return refuse("not a path")
+    if G == 0 or C == 0:
+        return refuse("empty")
+    if G == C:
+        return refuse("square")
+    if frame is not None:
+        if not frame.columns.is_unique:
+            return refuse("duplicate labels")
+        kinds = frame.dtypes.unique()
+        if len(kinds) > 1 and frame.iloc[:0, columns].to_numpy().dtype != frame.iloc[:0].to_numpy().dtype:
+            return refuse("mixed dtypes")
+    x = frame.to_numpy() if frame is not None else matrix_or_frame
+    if x.dtype.name not in _MTX_DTYPES:
+        return refuse(f"dtype {x.dtype}")
+    t = time.perf_counter()
+    x, code = _mtx_narrow(x)
+    info["narrow_s"] = time.perf_counter() - t
+    mi = _lib.MtxInfo()
+    t = time.perf_counter()
+    st = _lib.lib().cyto_mtx_write(path.encode(), G, N, x.ctypes.data, N, code, columns.ctypes.data, C, int(block_bytes), device_id,
+                                   ctypes.byref(mi))
+    info["library_s"] = time.perf_counter() - t
+    if st == _lib.CYTO_ERR_UNSUPPORTED:                                      # nothing is left at `path`
+        return refuse(_MTX_REFUSALS.get(mi.reason, str(mi.reason)))
+    _lib.check(st)
+    info.update(nnz=mi.nnz, bytes=mi.bytes, field="real" if mi.field else "integer", blocks=mi.blocks, upload_s=mi.ms_upload / 1e3,
+                kernels_s=mi.ms_kernels / 1e3, download_s=mi.ms_download / 1e3, write_s=mi.ms_write / 1e3)
+    info["total_s"] = time.perf_counter() - t0
+    return info if return_info else None
+
+
 def save_results(output_path, output_prefix, cell_ids_selected, all_cells_save, assigned_locations,
-                 cell_type_data, sampling_method, single_cell):
-    """post_processing.py:10-116, same arguments.  Writes
+                 cell_type_data, sampling_method, single_cell, device_id=None):
+    """post_processing.py:10-116, same arguments, and device_id: None writes matrix.mtx on the host (scipy); a device number has
+    write_mtx_device write it (the same bytes).  Writes
       <prefix>assigned_locations.csv
       <prefix>assigned_expression/{genes.tsv, barcodes.tsv, matrix.mtx}     (sampling_method "duplicates")
       <prefix>new_scRNA.csv                                                 ("place_holders": the generated cells)
@@ -52,14 +161,27 @@ def save_results(output_path, output_prefix, cell_ids_selected, all_cells_save, 
         if os.path.exists(out_dir):
             print("\033[91mWARNING\033[0m: {} exists and the expression matrix may be overwritten.".format(out_dir))
         os.makedirs(out_dir, exist_ok=True)
-        expr = all_cells_save.loc[:, ["CELL_{}".format(x) for x in df.OriginalCID]]
-        expr.index = _strip("GENE_", expr.index)
-        expr.columns = df.UniqueCID
-        genes = expr.index.to_frame()
-        genes.reset_index(inplace=True)           # gene id twice: Read10X expects the name in the second column
-        genes.to_csv(os.path.join(out_dir, "genes.tsv"), sep="\t", header=False, index=False)
-        expr.columns.to_frame().to_csv(os.path.join(out_dir, "barcodes.tsv"), sep="\t", header=False, index=False)
-        scipy.io.mmwrite(os.path.join(out_dir, "matrix.mtx"), scipy.sparse.coo_matrix(expr))
+        labels = ["CELL_{}".format(x) for x in df.OriginalCID]
+        positions = None
+        if device_id is not None and all_cells_save.columns.is_unique:
+            positions = all_cells_save.columns.get_indexer(labels)
+            if (positions < 0).any():                     # (a missing label: the host path raises its KeyError)
+                positions = None
+        if positions is None:
+            expr = all_cells_save.loc[:, labels]
+            expr.index = _strip("GENE_", expr.index)
+            expr.columns = df.UniqueCID
+            genes = expr.index.to_frame()
+            genes.reset_index(inplace=True)           # gene id twice: Read10X expects the name in the second column
+            genes.to_csv(os.path.join(out_dir, "genes.tsv"), sep="\t", header=False, index=False)
+            expr.columns.to_frame().to_csv(os.path.join(out_dir, "barcodes.tsv"), sep="\t", header=False, index=False)
+            scipy.io.mmwrite(os.path.join(out_dir, "matrix.mtx"), scipy.sparse.coo_matrix(expr))
+        else:                                         # the same three files without the gathered genes x cells frame
+            genes = pd.Index(_strip("GENE_", all_cells_save.index)).to_frame()
+            genes.reset_index(inplace=True)
+            genes.to_csv(os.path.join(out_dir, "genes.tsv"), sep="\t", header=False, index=False)
+            pd.Index(df.UniqueCID).to_frame().to_csv(os.path.join(out_dir, "barcodes.tsv"), sep="\t", header=False, index=False)
+            write_mtx_device(os.path.join(out_dir, "matrix.mtx"), all_cells_save, positions, device_id=device_id)
     else:
         generated = all_cells_save.loc[:, ~all_cells_save.columns.isin(cell_type_data.index)]
         generated.index = _strip("GENE_", generated.index.astype(str))

@@ -283,7 +283,7 @@ int cyto_comm_destroy(void *comm);
  * of these (0 and 1 mean what the name says; 2 and 3 came in round 6): raw counts are small integers, and a uint16 / uint8 matrix is a
  * half / a quarter of the float32 upload -- the transform kernels widen in their loads, the numbers are the same bit for bit. */
 enum { CYTO_DTYPE_F32 = 0, CYTO_DTYPE_F64 = 1, CYTO_DTYPE_U16 = 2, CYTO_DTYPE_U8 = 3, CYTO_DTYPE_I32 = 4, CYTO_DTYPE_I64 = 5 };
-/* (CYTO_DTYPE_I32 / _I64: integer count matrices of cyto_downsample only) */
+/* (CYTO_DTYPE_I32 / _I64: integer matrices of cyto_downsample and cyto_mtx_write only) */
 
 /* ---- A1: normalize_data (cytospace/common/common.py:142-147): nan_to_num, per-column counts per
  * million over the gene axis, log2(x + 1), nan_to_num.  x: G x C host matrix (float64 if x_is_f64
@@ -456,6 +456,41 @@ void cyto_table_free(cyto_table *t);
 /* The converter alone, on the host (a test hook): token i is text[offsets[i], offsets[i+1]); kinds[i] 0 integer token (ints[i],
  * and values[i] as a decimal), 1 decimal token (values[i]), 2 outside the token grammar, 3 out of range. */
 int cyto_table_parse_tokens(const char *text, int64_t n, const int64_t *offsets, double *values, int64_t *ints, int8_t *kinds);
+
+/* ---- the assigned-expression MatrixMarket file (cytospace_amd.post_processing.write_mtx_device): what
+ * scipy.io.mmwrite(path, coo_matrix(X[:, cols])) writes, byte for byte, formatted on the device.
+ * x: G x N host matrix (ldx) of any CYTO_DTYPE_*; cols: C source columns in [0, N), in file order, repeats allowed; G, C < 2^31.
+ * The field is "integer" for the integer types and "real" for float32 / float64 -- and "real" for any type when no
+ * entry is non-zero, as scipy has it.  block_bytes: the most text formatted per device
+ * buffer (whole genes; a gene with more text stands alone), 0 for the default (32 MiB).
+ * CYTO_ERR_UNSUPPORTED: info->reason says why, and nothing is left at `path` (as after any other failure):
+ * a real non-zero that is not finite, not an integer, or not below 2^53 (2^24 in a float32 matrix: scipy writes a float32's
+ * shortest digits, which above 2^24 are not the integer's own); G == C (scipy looks for symmetry in square matrices); the file cannot
+ * be created or written. */
+enum {
+    CYTO_MTX_ERR_FRACTION = 2,    /* a real value with a fractional part */
+    CYTO_MTX_ERR_NONFINITE = 3,   /* NaN or +-inf */
+    CYTO_MTX_ERR_MAGNITUDE = 4,   /* a real value of magnitude >= 2^53 (float32: >= 2^24) */
+    CYTO_MTX_ERR_SQUARE = 5,      /* G == C */
+    CYTO_MTX_ERR_IO = 6           /* open() or write() failed */
+};
+typedef struct cyto_mtx_info {
+    int64_t nnz, bytes;           /* entries written; bytes of the file, header included */
+    int64_t blocks;               /* device buffers the body took */
+    int32_t field;                /* 0 integer, 1 real (also: no entries) */
+    int32_t reason;               /* CYTO_MTX_ERR_* with CYTO_ERR_UNSUPPORTED, else 0 */
+    double ms_upload;             /* the matrix and the column list, host to device */
+    double ms_kernels;            /* the count pass (with its small copies) and the format launches (device events) */
+    double ms_download;           /* the blocks' copies into pinned memory (device events; they overlap the other phases) */
+    double ms_write;              /* write() calls */
+} cyto_mtx_info;
+int cyto_mtx_write(const char *path, int64_t G, int64_t N, const void *x, int64_t ldx, int x_dtype, const int64_t *cols, int64_t C,
+                   int64_t block_bytes, int device_id, cyto_mtx_info *info);
+/* The formatter alone, on the host (a test hook): entry i is (rows[i], cols[i], values[i]), 0-based, values of CYTO_DTYPE_* dtype; its
+ * line is out[offsets[i], offsets[i + 1]) -- empty for a zero, which the writer skips.  out holds 64 * n bytes, offsets n + 1 words.
+ * CYTO_ERR_UNSUPPORTED at the first real value outside the device grammar. */
+int cyto_mtx_format_entries(const int64_t *rows, const int64_t *cols, const void *values, int dtype, int64_t n, char *out,
+                            int64_t *offsets);
 
 #ifdef __cplusplus
 }
