@@ -1,10 +1,59 @@
 // lap_dev.h -- device helpers shared by the LAP kernels (lap_jv.hip: the chain solver; lap_wide.hip: the wide solver):
-// order-preserving float keys, DPP wave reductions, the LDS-only barrier, the row-cache constants.
+// the status block of a solve (LapStatus) with its counter and timer indices, order-preserving float keys, DPP wave reductions, the
+// LDS-only barrier, the row-cache constants.
 #pragma once
 #include "cyto_common.h"
 #include <math.h>
+#include <stddef.h>
 
 namespace cyto {
+
+// Counters of a solve (LapStatus::counters): the first ten by every solver, the rest by the cached chain and the lazy augmentation.
+enum { C_RT = 0, C_ARR, C_AUG_INIT, C_AUG_RELAX, C_AUGS, C_HOPS, C_FREE_CR, C_FREE_A1, C_FREE_A2, C_ROWS_READ, C_NCOUNTERS,
+       C2_DENSE_REFRESH = C_NCOUNTERS, C2_AUG_SKIPPED, C2_NCOUNTERS,
+       C2_AUG_DENSE = C2_NCOUNTERS, C2_AUG_SPARSE_INIT, C3_NCOUNTERS };
+// Counters of the wide solver (LapStatus::wide)
+enum { WC_ROUNDS = 0, WC_BIDS, WC_RETIRED, WC_ACTIVE_LEFT, WC_FREE_ARR, WC_DENSE_ARR, WC_DENSE_AUG, WC_AUG_ROUNDS, WC_AUG_PROCESSED,
+       WC_TRIVIAL, WC_VERIFY_PASSES, WC_AUG_LAUNCHES, WC_N };
+// What the wide kernels leave in LapStatus::timers: *_TICKS are 100 MHz ticks, the rest are counts.  A CYTO_WIDE_PROF build
+// OVERLAYS WT_ARR_LAUNCHES .. WT_PAR_BATCHES and WT_PAR_DISCARDED with the tick split of wide_arr's chain rounds, so
+// cyto_lap_info's wide_arr_launches, wide_scaled, wide_phases and wide_par_* are meaningless in such a build.
+enum { WT_LIST_ROUNDS = 0, WT_LIST_TICKS, WT_CHAIN_ROUNDS, WT_CHAIN_TICKS,      // wide_arr: its list rounds and its chain rounds
+       WT_DEALS, WT_ARR_SETUP_TICKS, WT_ARR_TAIL_TICKS,                         // wide_arr: re-deals of the chain rows; before / after the rounds
+       WT_PAR_DISCARDED,                                                        // wide_aug<PAR>: searches run and thrown away
+       WT_AUG_ROUNDS_TICKS, WT_AUG_VERIFY_TICKS, WT_AUG_FINISH_TICKS, WT_AUG_TRIVIAL_TICKS,     // wide_aug, by part of a search
+       WT_ARR_LAUNCHES, WT_SCALED, WT_PHASES,                                   // launches of wide_arr; eps-scaled? (0 / 1); phases begun
+       WT_PAR_BATCHES,                                                          // wide_aug<PAR>: batches of searches
+       WT_N };
+
+// The status block of one float32 / float64 solve: device memory that the kernels of both solvers write and the host drivers
+// (lap_jv.hip) zero before the solve and read back after it.
+struct LapStatus {
+    int nonfinite;                      // colred_partial: the cost holds a NaN or an infinity
+    int status;                         // != 0: the solve failed (the finishers of the chain, the lazy and the wide kernels)
+    double total;                       // the assignment's cost (finishers; exact_repair rewrites it)
+    long long counters[C3_NCOUNTERS];   // C_* / C2_*
+    int numfree;                        // rows still free before the augmentation (jv_chain2, wide_arr, the one-edge kernels)
+    int wide_done;                      // searches done, wide solver (wide_aug and the one-edge kernels)
+    int lazy_done;                      // searches completed by jv_aug_lazy (== numfree unless it gave up)
+    int pad0_;
+    int ngroups;                        // runs of identical rows (rows_group_ids)
+    int pad1_[3];
+    long long wide[WC_N];               // WC_*
+    long long timers[WT_N];             // WT_*
+    unsigned char arr[128];             // wide_arr's phase machine (lap_wide.hip: ArrHead)
+};
+static_assert(sizeof(LapStatus) == 512, "LapStatus layout");
+static_assert(offsetof(LapStatus, nonfinite) == 0 && offsetof(LapStatus, status) == 4 && offsetof(LapStatus, total) == 8, "LapStatus layout");
+static_assert(offsetof(LapStatus, counters) == 16 && offsetof(LapStatus, numfree) == 128, "LapStatus layout");
+static_assert(offsetof(LapStatus, wide_done) == 132 && offsetof(LapStatus, lazy_done) == 136, "LapStatus layout");
+static_assert(offsetof(LapStatus, ngroups) == 144 && offsetof(LapStatus, wide) == 160, "LapStatus layout");
+static_assert(offsetof(LapStatus, timers) == 256 && offsetof(LapStatus, arr) == 384, "LapStatus layout");
+static_assert(C3_NCOUNTERS * 8 + 16 <= offsetof(LapStatus, numfree), "a new counter would overwrite numfree");
+static_assert(WC_N * 8 + 160 <= offsetof(LapStatus, timers), "a new wide counter would overwrite the timers");
+static_assert(WT_N == 16 && WT_N * 8 + 256 <= offsetof(LapStatus, arr), "a new timer would overwrite wide_arr's state");
+// The kernels' argument blocks keep the block as char *misc (their mirror structs retype every pointer field)
+__host__ __device__ __forceinline__ LapStatus *lap_status(char *misc) { return reinterpret_cast<LapStatus *>(misc); }
 
 constexpr int KC = 64;             // cache slots per row (one per lane of a wave)
 constexpr int KCU = 63;            // usable entries; slot 63 = { COLSENT, floor }

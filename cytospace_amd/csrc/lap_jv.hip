@@ -43,9 +43,6 @@ namespace cyto {
 constexpr int BLOCK = 1024;
 constexpr int NW = BLOCK / 64;
 
-// counters written by jv_chain (index into ChainState::counters)
-enum { C_RT = 0, C_ARR, C_AUG_INIT, C_AUG_RELAX, C_AUGS, C_HOPS, C_FREE_CR, C_FREE_A1, C_FREE_A2, C_ROWS_READ, C_NCOUNTERS };
-
 template <typename T> struct VecOf;
 template <> struct VecOf<float> { using type = float4; static constexpr int W = 4; };
 template <> struct VecOf<double> { using type = double2; static constexpr int W = 2; };
@@ -1084,7 +1081,6 @@ __global__ __launch_bounds__(BLOCK) void jv_chain_stream(ChainArgs<T> a) {
 constexpr int BLOCK2 = 512;        // 8 waves: 256 VGPRs per lane for the column-resident state
 constexpr int NW2 = BLOCK2 / 64;
 enum { OP_EXIT = 0, OP_REFRESH = 1, OP_AUG = 2 };
-enum { C2_DENSE_REFRESH = C_NCOUNTERS, C2_AUG_SKIPPED, C2_NCOUNTERS };
 
 // a wave's candidate for the next pick of the dense augmentation, with everything the step needs once it wins
 struct __attribute__((aligned(16))) PickRec { uint64_t key; int32_t row; float h; float vjp; int32_t g; int32_t skip; int32_t srow; };   // srow: the stored row (row map applied)
@@ -1707,7 +1703,7 @@ __global__ __launch_bounds__(64 * CBW) void build_row_caches_wave(int n, int64_t
 // memory are generic to the compiler, and every access through them would be a FLAT instruction instead of a global one.
 //   fws        float workspace: v[n] | u[n] | sumvd[n] | cassign[n] (= c[colsol[j]][j]) | 2n more
 //   iws        int workspace: rowsol | colsol | matches | freerows | rtrows | pred | colgroup | ...   (n each)
-//   cache_*    [n][KC] row caches;  misc: +8 double total; +16 long long counters[]; +4 int status
+//   cache_*    [n][KC] row caches;  misc: the status block (lap_dev.h: LapStatus)
 //   rowgid     [n] duplicate-row group of every row (consecutive identical rows share an id)
 //   rowmap     [n] stored row of every LAP row, or nullptr (row i is stored row i)
 //   g_hbest / g_hstamp   [ngroups] scratch for gmode 2 (stamps zeroed)
@@ -2353,11 +2349,11 @@ __global__ __launch_bounds__(BLOCK2) void jv_chain2(const Chain2Args *__restrict
         }
     }
     if (tid == 0) {
-        long long *counters = reinterpret_cast<long long *>(a.misc + 16);
+        long long *counters = lap_status(a.misc)->counters;
         counters[C_RT] = c_rt; counters[C_ARR] = c_arr;
         counters[C_FREE_CR] = c_free_cr; counters[C_FREE_A1] = c_free_a1; counters[C_FREE_A2] = c_free_a2;
         counters[C2_DENSE_REFRESH] = c_dense;
-        *reinterpret_cast<int *>(a.misc + 128) = numfree;
+        lap_status(a.misc)->numfree = numfree;
     }
 }
 
@@ -2425,11 +2421,11 @@ __global__ __launch_bounds__(BS) void jv_aug2(const Chain2Args *__restrict__ bat
         for (int c = tid; c < n; c += BS) { s_ca[c] = cassign[c]; s_cg[c] = (uint16_t)(gmode ? colgroup[c] : 0); }
     }
     __syncthreads();
-    const int numfree = *reinterpret_cast<const int *>(a.misc + 128);
+    const int numfree = lap_status(a.misc)->numfree;
     long long c_relax = 0, c_hops = 0, c_augs = 0, c_skipped = 0;
     long long rows0 = 0, base0 = 0;
     if (a.aug_start > 0) {   // carry the counters of the searches jv_aug_lazy completed
-        const long long *cn = reinterpret_cast<const long long *>(a.misc + 16);
+        const long long *cn = lap_status(a.misc)->counters;
         c_relax = cn[C_AUG_RELAX]; c_hops = cn[C_HOPS]; c_augs = cn[C_AUGS]; c_skipped = cn[C2_AUG_SKIPPED];
         rows0 = cn[C_ROWS_READ]; base0 = c_augs + c_relax - c_skipped;
     }
@@ -2471,13 +2467,13 @@ __global__ __launch_bounds__(BS) void jv_aug2(const Chain2Args *__restrict__ bat
     if (tid == 0) {
         double t = 0.0;
         for (int w = 0; w < BS / 64; w++) t += s.sum[w];
-        *reinterpret_cast<double *>(a.misc + 8) = t;
-        long long *counters = reinterpret_cast<long long *>(a.misc + 16);
+        lap_status(a.misc)->total = t;
+        long long *counters = lap_status(a.misc)->counters;
         counters[C_AUG_INIT] = c_augs; counters[C_AUG_RELAX] = c_relax; counters[C_AUGS] = c_augs; counters[C_HOPS] = c_hops;
         counters[C_ROWS_READ] = a.aug_start > 0 ? rows0 + (c_augs + c_relax - c_skipped - base0)
                                                 : counters[C2_DENSE_REFRESH] + c_augs + c_relax - c_skipped;
         counters[C2_AUG_SKIPPED] = c_skipped;
-        *reinterpret_cast<int *>(a.misc + 4) = err;
+        lap_status(a.misc)->status = err;
     }
 }
 #undef SLOT_COL
@@ -2529,7 +2525,6 @@ __device__ __forceinline__ LazyArgs load_args(const LazyArgs *__restrict__ batch
 }
 struct LazyCmd { int op, row, step, stamp; float h; };
 enum { LZ_DENSE = 1, LZ_EXIT = 2, LZ_ERR = 3, LZ_INIT_DENSE = 4 };
-enum { C2_AUG_DENSE = C2_NCOUNTERS, C2_AUG_SPARSE_INIT, C3_NCOUNTERS };
 constexpr int LZ_MAXEXC = 64;
 
 __device__ __forceinline__ void lds_min_u64(uint64_t *p, uint64_t x) {
@@ -2631,7 +2626,7 @@ __global__ __launch_bounds__(BLOCK2) void jv_aug_lazy(const LazyArgs *__restrict
     for (int b = tid; b < nbp; b += BLOCK2) bmin[b] = KEYMAX;
     for (int w = tid; w < 2 * nb; w += BLOCK2) s_sc[w] = 0;
     __syncthreads();
-    const int numfree = *reinterpret_cast<const int *>(a.misc + 128);
+    const int numfree = lap_status(a.misc)->numfree;
     long long c_relax = 0, c_hops = 0, c_augs = 0, c_skipped = 0, c_dense = 0;
     int err = 0;
     const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(gv, 0, nquad * 16, 0x00020000);
@@ -3091,15 +3086,15 @@ __global__ __launch_bounds__(BLOCK2) void jv_aug_lazy(const LazyArgs *__restrict
     if (tid == 0) {
         double t = 0.0;
         for (int w = 0; w < NW2; w++) t += s.sum[w];
-        *reinterpret_cast<double *>(a.misc + 8) = t;
-        long long *counters = reinterpret_cast<long long *>(a.misc + 16);
+        lap_status(a.misc)->total = t;
+        long long *counters = lap_status(a.misc)->counters;
         counters[C_AUG_INIT] = c_augs; counters[C_AUG_RELAX] = c_relax; counters[C_AUGS] = c_augs; counters[C_HOPS] = c_hops;
         counters[C_ROWS_READ] = counters[C2_DENSE_REFRESH] + (c_augs - c_sparse) + c_dense;
         counters[C2_AUG_SKIPPED] = c_skipped;
         counters[C2_AUG_DENSE] = c_dense;
         counters[C2_AUG_SPARSE_INIT] = c_sparse;
-        *reinterpret_cast<int *>(a.misc + 136) = f;          // searches completed (== numfree unless the kernel gave up)
-        *reinterpret_cast<int *>(a.misc + 4) = err;
+        lap_status(a.misc)->lazy_done = f;
+        lap_status(a.misc)->status = err;
     }
 }
 
@@ -3384,10 +3379,12 @@ struct F32Job {
     DevBuf b_rowmap, b_ulist, b_ufirst, b_wide;
     int nused = 0;
     const float *dcost = nullptr; int64_t dld = 0;
-    int h_nonfinite = 0, h_ngroups = 0, h_hand[3] = {0, 0, 0};
+    int h_nonfinite = 0, h_ngroups = 0;
+    LapStatus h_hand = {};      // numfree .. lazy_done, when jv_aug_lazy may have given up
     Chain2Args c2; LazyArgs la;
     size_t shm_lazy = 0, shm_aug = 0;
     bool alive() const { return status == CYTO_OK; }
+    LapStatus *st() const { return b_misc.as<LapStatus>(); }
     const int32_t *rowmap() const { return rowmap_host ? b_rowmap.as<int32_t>() : nullptr; }
     const int32_t *same(int n) const { return (h_ngroups < n && n >= 2) ? b_same.as<int32_t>() : nullptr; }    // (runs of identical rows)
 };
@@ -3480,17 +3477,19 @@ static int launch_batch(const F32Plan &pl, std::vector<F32Job> &jobs, hipStream_
     hipLaunchKernelGGL(lk, dim3(nl), dim3(BLOCK2), shm_lazy, stream, d_la.as<LazyArgs>());
     CYTO_HIP(hipGetLastError());
     if constexpr (LDS_STATE) {
-        // which searches gave up?  (misc + 128: number of free rows, misc + 136: searches completed)
+        // which searches gave up?
+        constexpr size_t h0 = offsetof(LapStatus, numfree), h1 = offsetof(LapStatus, lazy_done) + sizeof(int);
         bool any_bail = false;
         for (int k = 0; k < nl; k++) any_bail |= h_la[k].may_bail != 0;
         if (any_bail) {
             for (int k = 0; k < nl; k++)
-                CYTO_HIP(hipMemcpyAsync(jobs[live[k]].h_hand, jobs[live[k]].c2.misc + 128, sizeof(int) * 3, hipMemcpyDeviceToHost, stream));
+                CYTO_HIP(hipMemcpyAsync(reinterpret_cast<char *>(&jobs[live[k]].h_hand) + h0, jobs[live[k]].c2.misc + h0, h1 - h0, hipMemcpyDeviceToHost,
+                                        stream));
             CYTO_HIP(hipStreamSynchronize(stream));
             std::vector<Chain2Args> cont;
             for (int k = 0; k < nl; k++) {
                 const F32Job &j = jobs[live[k]];
-                if (h_la[k].may_bail && j.h_hand[2] < j.h_hand[0]) { Chain2Args a = h_c2[k]; a.aug_start = j.h_hand[2]; cont.push_back(a); }
+                if (h_la[k].may_bail && j.h_hand.lazy_done < j.h_hand.numfree) { Chain2Args a = h_c2[k]; a.aug_start = j.h_hand.lazy_done; cont.push_back(a); }
             }
             if (!cont.empty()) {
                 // (the first nl blocks of d_c2 are no longer read: jv_chain2 has finished)
@@ -3634,7 +3633,7 @@ static int exact_repair(ExactRun &ex, int n, F32Job &j, double gap, int grid, hi
         std::vector<float> u((size_t)n);
         double total = 0.0;
         CYTO_HIP(hipMemcpyAsync(u.data(), d_v + n, nI, hipMemcpyDeviceToHost, stream));
-        CYTO_HIP(hipMemcpyAsync(&total, j.b_misc.as<char>() + 8, sizeof total, hipMemcpyDeviceToHost, stream));
+        CYTO_HIP(hipMemcpyAsync(&total, &j.st()->total, sizeof total, hipMemcpyDeviceToHost, stream));
         CYTO_HIP(hipStreamSynchronize(stream));
         double delta = 0.0;
         for (int i = 0; i < n; i++) {
@@ -3650,11 +3649,25 @@ static int exact_repair(ExactRun &ex, int n, F32Job &j, double gap, int grid, hi
         for (int i = 0; i < n; i++) { both[(size_t)i] = sigma[(size_t)i]; both[(size_t)n + sigma[(size_t)i]] = i; }
         CYTO_HIP(hipMemcpyAsync(d_rowsol, both.data(), 2 * nI, hipMemcpyHostToDevice, stream));
         CYTO_HIP(hipMemcpyAsync(d_v + n, u.data(), nI, hipMemcpyHostToDevice, stream));
-        CYTO_HIP(hipMemcpyAsync(j.b_misc.as<char>() + 8, &total, sizeof total, hipMemcpyHostToDevice, stream));
+        CYTO_HIP(hipMemcpyAsync(&j.st()->total, &total, sizeof total, hipMemcpyHostToDevice, stream));
         CYTO_HIP(hipStreamSynchronize(stream));
     }
     ex.ms_repair = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return CYTO_OK;
+}
+
+// the counters every solver keeps, as cyto_lap_info reports them
+static void info_from_counters(cyto_lap_info *info, int n, const LapStatus &h) {
+    info->scans_colred = n;
+    info->scans_redtransfer = h.counters[C_RT];
+    info->scans_arr = h.counters[C_ARR];
+    info->scans_aug_init = h.counters[C_AUG_INIT];
+    info->scans_aug_relax = h.counters[C_AUG_RELAX];
+    info->augmentations = h.counters[C_AUGS];
+    info->path_hops = h.counters[C_HOPS];
+    info->free_after_colred = h.counters[C_FREE_CR];
+    info->free_after_arr1 = h.counters[C_FREE_A1];
+    info->free_after_arr2 = h.counters[C_FREE_A2];
 }
 
 // All problems have the same n.  jobs[b].status carries per-problem failures (non-finite costs, solver status); the
@@ -3762,7 +3775,7 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
             size_t off = 0;
             auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
             const size_t o_fws = take(6 * nT + 64), o_iws = take(10 * nI + 64), o_imin = take(nI), o_pmin = take((size_t)pl.rowblocks * nT),
-                         o_parg = take((size_t)pl.rowblocks * nI), o_misc = take(512), o_same = take(nI), o_gid = take(nI),
+                         o_parg = take((size_t)pl.rowblocks * nI), o_misc = take(sizeof(LapStatus)), o_same = take(nI), o_gid = take(nI),
                          o_ccol = take((size_t)n * KC * sizeof(uint32_t)), o_cval = take((size_t)n * KC * sizeof(float));
             if ((rc = j.slab.alloc(off, stream))) return rc;
             char *base = j.slab.as<char>();
@@ -3774,8 +3787,7 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
         // float workspace: v | u | ... ; int workspace: rowsol | colsol | matches | freerows | rtrows | pred | ...
         float *d_v = j.b_fws.as<float>();
         int32_t *d_rowsol = j.b_iws.as<int32_t>(), *d_colsol = d_rowsol + n, *d_matches = d_rowsol + 2 * (size_t)n;
-        // misc: [0] nonfinite flag (int), [1] chain status (int), [8..16) total (double), [16..) counters, [144] ngroups
-        CYTO_HIP(hipMemsetAsync(j.b_misc.p, 0, 512, stream));
+        CYTO_HIP(hipMemsetAsync(j.b_misc.p, 0, sizeof(LapStatus), stream));
         CYTO_HIP(hipMemsetAsync(d_rowsol, 0xFF, nI, stream));
         CYTO_HIP(hipMemsetAsync(d_matches, 0, nI, stream));
         {   // the column minima need every DISTINCT row once: with a row map only the stored rows in use are swept
@@ -3783,7 +3795,7 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
             const int rpb = j.rowmap_host ? (nrows + pl.rowblocks - 1) / pl.rowblocks : pl.rows_per_block;
             const int rblocks = j.rowmap_host ? (nrows + rpb - 1) / rpb : pl.rowblocks;
             hipLaunchKernelGGL(colred_partial<float>, dim3(pl.colblocks, rblocks), dim3(256), 0, stream, n, j.dld, j.dcost, rpb,
-                               j.b_pmin.as<float>(), j.b_parg.as<int32_t>(), j.b_misc.as<int>(), nrows,
+                               j.b_pmin.as<float>(), j.b_parg.as<int32_t>(), &j.st()->nonfinite, nrows,
                                j.rowmap_host ? j.b_ulist.as<int32_t>() : (const int32_t *)nullptr,
                                j.rowmap_host ? j.b_ufirst.as<int32_t>() : (const int32_t *)nullptr);
             hipLaunchKernelGGL(colred_finish<float>, dim3((n + 255) / 256), dim3(256), 0, stream, n, rblocks, j.b_pmin.as<float>(),
@@ -3804,11 +3816,11 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
             else
                 hipLaunchKernelGGL(rows_same_as_prev<float>, dim3(min(n, 2048)), dim3(256), 0, stream, n, j.dld, j.dcost, j.b_same.as<int32_t>());
             hipLaunchKernelGGL(rows_group_ids, dim3(1), dim3(1024), 0, stream, n, j.b_same.as<int32_t>(), j.b_gid.as<int32_t>(),
-                               j.b_misc.as<int>() + 36);   // misc + 144
+                               &j.st()->ngroups);
         }
         // a non-finite cost makes every later comparison meaningless: that problem stops before the chain
-        CYTO_HIP(hipMemcpyAsync(&j.h_nonfinite, j.b_misc.as<int>(), sizeof(int), hipMemcpyDeviceToHost, stream));
-        if (want_groups) CYTO_HIP(hipMemcpyAsync(&j.h_ngroups, j.b_misc.as<int>() + 36, sizeof(int), hipMemcpyDeviceToHost, stream));
+        CYTO_HIP(hipMemcpyAsync(&j.h_nonfinite, &j.st()->nonfinite, sizeof(int), hipMemcpyDeviceToHost, stream));
+        if (want_groups) CYTO_HIP(hipMemcpyAsync(&j.h_ngroups, &j.st()->ngroups, sizeof(int), hipMemcpyDeviceToHost, stream));
     }
     CYTO_HIP(hipGetLastError());
     CYTO_HIP(hipStreamSynchronize(stream));
@@ -3906,15 +3918,13 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
     }
     for (F32Job &j : jobs) {
         if (!j.alive()) continue;
-        int h_status = 0;
-        long long h_counters[C3_NCOUNTERS] = {0};
+        LapStatus h;
         int32_t *d_rowsol = j.b_iws.as<int32_t>();
         float *d_v = j.b_fws.as<float>();
-        CYTO_HIP(hipMemcpy(&h_status, j.b_misc.as<int>() + 1, sizeof(int), hipMemcpyDeviceToHost));
-        CYTO_HIP(hipMemcpy(h_counters, j.b_misc.as<char>() + 16, sizeof(h_counters), hipMemcpyDeviceToHost));
+        CYTO_HIP(hipMemcpy(&h, j.st(), sizeof h, hipMemcpyDeviceToHost));
         double h_gap[3] = {-1.0, -1.0, -1.0};
         ExactRun ex;
-        if (((opts.certify && j.info) || opts.exact) && !h_status) {
+        if (((opts.certify && j.info) || opts.exact) && !h.status) {
             // the float64 certificate (above): one more streaming pass, on the stream, behind the solve
             DevBuf b_viol;
             if ((rc = b_viol.alloc(((size_t)n + 4) * sizeof(double), stream))) return rc;
@@ -3933,34 +3943,20 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
         if (j.colsol) CYTO_HIP(hipMemcpy(j.colsol, d_rowsol + n, nI, hipMemcpyDeviceToHost));
         if (j.u) CYTO_HIP(hipMemcpy(j.u, d_v + n, nT, hipMemcpyDeviceToHost));
         if (j.v) CYTO_HIP(hipMemcpy(j.v, d_v, nT, hipMemcpyDeviceToHost));
-        if (j.total) CYTO_HIP(hipMemcpy(j.total, j.b_misc.as<char>() + 8, sizeof(double), hipMemcpyDeviceToHost));
+        if (j.total) CYTO_HIP(hipMemcpy(j.total, &j.st()->total, sizeof(double), hipMemcpyDeviceToHost));   // (exact_repair rewrites it)
         if (j.info) {
             cyto_lap_info *info = j.info;
             memset(info, 0, sizeof *info);
             // (kernel times of a batch are those of the whole batch: its problems share every launch)
             info->ms_colred = ms_colred; info->ms_cache = ms_cache; info->ms_chain = ms_chain; info->ms_arr = ms_arr; info->ms_aug = ms_aug;
             info->ms_total = info->ms_colred + info->ms_cache + info->ms_chain;
-            info->scans_colred = n;
-            info->scans_redtransfer = h_counters[C_RT];
-            info->scans_arr = h_counters[C_ARR];
-            info->scans_aug_init = h_counters[C_AUG_INIT];
-            info->scans_aug_relax = h_counters[C_AUG_RELAX];
-            info->augmentations = h_counters[C_AUGS];
-            info->path_hops = h_counters[C_HOPS];
-            info->free_after_colred = h_counters[C_FREE_CR];
-            info->free_after_arr1 = h_counters[C_FREE_A1];
-            info->free_after_arr2 = h_counters[C_FREE_A2];
-            info->hbm_row_reads = 2 * (int64_t)n + h_counters[C_ROWS_READ];
-            info->dense_refreshes = h_counters[C2_DENSE_REFRESH];
-            info->aug_scans_skipped = h_counters[C2_AUG_SKIPPED];
-            info->aug_dense_scans = h_counters[C2_AUG_DENSE];
-            info->aug_sparse_inits = h_counters[C2_AUG_SPARSE_INIT];
-            info->aug_handover = -1;
-            if (pl.lazy && !pl.wide) {
-                int h[3] = {0, 0, 0};
-                CYTO_HIP(hipMemcpy(h, j.b_misc.as<char>() + 128, sizeof h, hipMemcpyDeviceToHost));
-                if (h[2] < h[0]) info->aug_handover = h[2];
-            }
+            info_from_counters(info, n, h);
+            info->hbm_row_reads = 2 * (int64_t)n + h.counters[C_ROWS_READ];
+            info->dense_refreshes = h.counters[C2_DENSE_REFRESH];
+            info->aug_scans_skipped = h.counters[C2_AUG_SKIPPED];
+            info->aug_dense_scans = h.counters[C2_AUG_DENSE];
+            info->aug_sparse_inits = h.counters[C2_AUG_SPARSE_INIT];
+            info->aug_handover = (pl.lazy && !pl.wide && h.lazy_done < h.numfree) ? h.lazy_done : -1;
             info->row_groups = j.h_ngroups;
             info->certified = h_gap[0] >= 0.0 ? 1 : 0;
             info->gap_f64 = h_gap[0] >= 0.0 ? h_gap[0] : 0.0; info->gap_max_f64 = h_gap[0] >= 0.0 ? h_gap[1] : 0.0;
@@ -3969,25 +3965,20 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
             info->exact_changed_rows = ex.changed; info->exact_overflow_rows = ex.overflow;
             info->exact_ms_emit = ex.ms_emit; info->exact_ms_repair = ex.ms_repair;
             if (pl.wide) {
-                long long wc[WC_N] = {0};
-                CYTO_HIP(hipMemcpy(wc, j.b_misc.as<char>() + 160, sizeof wc, hipMemcpyDeviceToHost));
+                const long long *wc = h.wide, *tm = h.timers;       // (timers: diagnostics for tools/wide_large.py; 100 MHz ticks)
                 info->wide = 1;
                 info->wide_rounds = wc[WC_ROUNDS]; info->wide_retired = wc[WC_RETIRED]; info->wide_dense_arr = wc[WC_DENSE_ARR];
                 info->wide_dense_aug = wc[WC_DENSE_AUG]; info->wide_aug_rounds = wc[WC_AUG_ROUNDS]; info->wide_aug_settled = wc[WC_AUG_PROCESSED];
                 info->wide_trivial = wc[WC_TRIVIAL]; info->wide_verify_passes = wc[WC_VERIFY_PASSES]; info->wide_aug_launches = wc[WC_AUG_LAUNCHES];
-                {   // phase timers the wide kernels keep (100 MHz ticks at misc + 256): diagnostics for tools/wide_large.py
-                    long long dbg[16] = {0};
-                    CYTO_HIP(hipMemcpy(dbg, j.b_misc.as<char>() + 256, sizeof dbg, hipMemcpyDeviceToHost));
-                    info->wide_list_rounds = dbg[0]; info->wide_chain_rounds = dbg[2];
-                    info->wide_ms_list = dbg[1] * 1e-5; info->wide_ms_chain = dbg[3] * 1e-5;
-                    info->wide_ms_aug_rounds = dbg[8] * 1e-5; info->wide_ms_aug_verify = dbg[9] * 1e-5;
-                    info->wide_ms_aug_finish = dbg[10] * 1e-5; info->wide_ms_aug_trivial = dbg[11] * 1e-5;
-                    info->wide_arr_launches = dbg[12]; info->wide_scaled = dbg[13]; info->wide_phases = dbg[14];
-                    info->wide_par_batches = dbg[15]; info->wide_par_discarded = dbg[7];
-                }
+                info->wide_list_rounds = tm[WT_LIST_ROUNDS]; info->wide_chain_rounds = tm[WT_CHAIN_ROUNDS];
+                info->wide_ms_list = tm[WT_LIST_TICKS] * 1e-5; info->wide_ms_chain = tm[WT_CHAIN_TICKS] * 1e-5;
+                info->wide_ms_aug_rounds = tm[WT_AUG_ROUNDS_TICKS] * 1e-5; info->wide_ms_aug_verify = tm[WT_AUG_VERIFY_TICKS] * 1e-5;
+                info->wide_ms_aug_finish = tm[WT_AUG_FINISH_TICKS] * 1e-5; info->wide_ms_aug_trivial = tm[WT_AUG_TRIVIAL_TICKS] * 1e-5;
+                info->wide_arr_launches = tm[WT_ARR_LAUNCHES]; info->wide_scaled = tm[WT_SCALED]; info->wide_phases = tm[WT_PHASES];
+                info->wide_par_batches = tm[WT_PAR_BATCHES]; info->wide_par_discarded = tm[WT_PAR_DISCARDED];
             }
         }
-        if (h_status) j.status = CYTO_ERR_INTERNAL;
+        if (h.status) j.status = CYTO_ERR_INTERNAL;
         if (ex.status == 3 && j.alive()) {
             // E over its cap: the float64 polish of this problem (one at a time in a batch: it widens the whole matrix)
             double ms = 0.0;
@@ -4063,19 +4054,19 @@ static int lap_solve_f64(int n, const double *cost, int64_t ld, int cost_on_devi
     const size_t nT = (size_t)n * sizeof(T), nI = (size_t)n * sizeof(int32_t);
     if ((rc = b_fws.alloc(6 * nT + 64, stream)) || (rc = b_iws.alloc(10 * nI + 64, stream)) || (rc = b_imin.alloc(nI, stream)) ||
         (rc = b_pmin.alloc((size_t)rowblocks * nT, stream)) || (rc = b_parg.alloc((size_t)rowblocks * nI, stream)) ||
-        (rc = b_misc.alloc(256, stream)))
+        (rc = b_misc.alloc(sizeof(LapStatus), stream)))
         return rc;
     T *d_v = b_fws.as<T>(), *d_u = b_fws.as<T>() + n;
     int32_t *d_rowsol = b_iws.as<int32_t>(), *d_colsol = d_rowsol + n, *d_matches = d_rowsol + 2 * (size_t)n;
-    int *d_nonfinite = b_misc.as<int>();
-    CYTO_HIP(hipMemsetAsync(b_misc.p, 0, 256, stream));
+    LapStatus *st = b_misc.as<LapStatus>();
+    CYTO_HIP(hipMemsetAsync(st, 0, sizeof(LapStatus), stream));
     CYTO_HIP(hipMemsetAsync(d_rowsol, 0xFF, nI, stream));
     CYTO_HIP(hipMemsetAsync(d_matches, 0, nI, stream));
     CYTO_HIP(hipEventRecord(e0, stream));
     hipLaunchKernelGGL(colred_partial<T>, dim3(colblocks, rowblocks), dim3(256), 0, stream, n, dld, dcost, rows_per_block,
-                       b_pmin.as<T>(), b_parg.as<int32_t>(), d_nonfinite, n, (const int32_t *)nullptr, (const int32_t *)nullptr);
+                       b_pmin.as<T>(), b_parg.as<int32_t>(), &st->nonfinite, n, (const int32_t *)nullptr, (const int32_t *)nullptr);
     int h_nonfinite = 0;
-    CYTO_HIP(hipMemcpyAsync(&h_nonfinite, d_nonfinite, sizeof(int), hipMemcpyDeviceToHost, stream));
+    CYTO_HIP(hipMemcpyAsync(&h_nonfinite, &st->nonfinite, sizeof(int), hipMemcpyDeviceToHost, stream));
     CYTO_HIP(hipStreamSynchronize(stream));
     if (h_nonfinite) return CYTO_ERR_NONFINITE;
     bool warm = opts.mode != 1 && opts.chain_variant == 0 && opts.augmentation == 0 && n >= 2;
@@ -4119,9 +4110,7 @@ static int lap_solve_f64(int n, const double *cost, int64_t ld, int cost_on_devi
     ca.n = n; ca.ld = dld; ca.cost = dcost; ca.v = d_v; ca.u = d_u;
     ca.rowsol = d_rowsol; ca.colsol = d_colsol; ca.matches = d_matches;
     ca.freerows = d_rowsol + 3 * (size_t)n; ca.rtrows = d_rowsol + 4 * (size_t)n; ca.pred = d_rowsol + 5 * (size_t)n;
-    ca.total = reinterpret_cast<double *>(b_misc.as<char>() + 8);
-    ca.counters = reinterpret_cast<long long *>(b_misc.as<char>() + 16);
-    ca.status = b_misc.as<int>() + 1;
+    ca.total = &st->total; ca.counters = st->counters; ca.status = &st->status;
     ca.dwork = d_v + 4 * (size_t)n; ca.lvl = d_rowsol + 7 * (size_t)n;
     ca.cache_col = nullptr; ca.cache_val = nullptr; ca.cs_lds = 0; ca.v_lds = 0;
     // register-resident chain while it does not spill (n <= 4096), else everything streams from L2 -- with row caches
@@ -4148,15 +4137,13 @@ static int lap_solve_f64(int n, const double *cost, int64_t ld, int cost_on_devi
     if (rc) return rc;
     CYTO_HIP(hipEventRecord(e2, stream));
     CYTO_HIP(hipStreamSynchronize(stream));
-    int h_status = 0;
-    long long h_counters[C_NCOUNTERS] = {0};
-    CYTO_HIP(hipMemcpy(&h_status, ca.status, sizeof(int), hipMemcpyDeviceToHost));
-    CYTO_HIP(hipMemcpy(h_counters, ca.counters, sizeof(h_counters), hipMemcpyDeviceToHost));
+    LapStatus h;
+    CYTO_HIP(hipMemcpy(&h, st, sizeof h, hipMemcpyDeviceToHost));
     if (rowsol) CYTO_HIP(hipMemcpy(rowsol, d_rowsol, nI, hipMemcpyDeviceToHost));
     if (colsol) CYTO_HIP(hipMemcpy(colsol, d_colsol, nI, hipMemcpyDeviceToHost));
     if (u) CYTO_HIP(hipMemcpy(u, d_u, nT, hipMemcpyDeviceToHost));
     if (v) CYTO_HIP(hipMemcpy(v, d_v, nT, hipMemcpyDeviceToHost));
-    if (total) CYTO_HIP(hipMemcpy(total, ca.total, sizeof(double), hipMemcpyDeviceToHost));
+    if (total) *total = h.total;
     if (info) {
         memset(info, 0, sizeof *info);
         float ms = 0;
@@ -4164,21 +4151,12 @@ static int lap_solve_f64(int n, const double *cost, int64_t ld, int cost_on_devi
         (void)hipEventElapsedTime(&ms, e1, e2); info->ms_chain = ms;
         info->ms_total = info->ms_colred + info->ms_chain;
         info->f64_warm = warm ? 1 : 0; info->f64_warm_ms = ms_warm;
-        info->scans_colred = n;
-        info->scans_redtransfer = h_counters[C_RT];
-        info->scans_arr = h_counters[C_ARR];
-        info->scans_aug_init = h_counters[C_AUG_INIT];
-        info->scans_aug_relax = h_counters[C_AUG_RELAX];
-        info->augmentations = h_counters[C_AUGS];
-        info->path_hops = h_counters[C_HOPS];
-        info->free_after_colred = h_counters[C_FREE_CR];
-        info->free_after_arr1 = h_counters[C_FREE_A1];
-        info->free_after_arr2 = h_counters[C_FREE_A2];
-        info->hbm_row_reads = n + h_counters[C_ROWS_READ];
+        info_from_counters(info, n, h);
+        info->hbm_row_reads = n + h.counters[C_ROWS_READ];
         info->aug_handover = -1;
         info->row_groups = n;
     }
-    return h_status ? CYTO_ERR_INTERNAL : CYTO_OK;
+    return h.status ? CYTO_ERR_INTERNAL : CYTO_OK;
 }
 
 // The float64 POLISH of a float32 solve (cyto_lap_opts.polish): the float32 solvers compare rounded reduced costs, so on a near-tie
@@ -4223,7 +4201,7 @@ static int lap_polish_f64(int n, const float *cost, int64_t ld, int cost_on_devi
     CYTO_HIP(hipStreamSynchronize(stream));
     staged.reset();
     std::vector<double> u64((size_t)n), v64((size_t)n);
-    cyto_lap_info li;
+    cyto_lap_info li = {};
     rc = lap_solve_f64(n, d64.as<double>(), ldd, 1, rowsol, colsol, u64.data(), v64.data(), total, &li, device_id, stream, k_default_opts, v32);
     if (rc) return rc;
     if (u) for (int i = 0; i < n; i++) u[i] = (float)u64[(size_t)i];
@@ -4240,7 +4218,7 @@ static int lap_solve_f32_one(int n, const float *cost, int64_t ld, int cost_on_d
     std::vector<F32Job> jobs(1);
     F32Job &j = jobs[0];
     j.cost = cost; j.ld = ld; j.cost_on_device = cost_on_device; j.rowmap_host = rowmap_host; j.nu = nu;
-    cyto_lap_info li;
+    cyto_lap_info li = {};
     std::vector<float> v_keep;
     cyto_lap_opts o = opts;
     if (opts.polish) { o.certify = 1; if (!v) { v_keep.resize((size_t)n); v = v_keep.data(); } }

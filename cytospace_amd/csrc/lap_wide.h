@@ -5,10 +5,6 @@
 
 namespace cyto {
 
-// wide counters (long long each) at misc + 160
-enum { WC_ROUNDS = 0, WC_BIDS, WC_RETIRED, WC_ACTIVE_LEFT, WC_FREE_ARR, WC_DENSE_ARR, WC_DENSE_AUG, WC_AUG_ROUNDS, WC_AUG_PROCESSED,
-       WC_TRIVIAL, WC_VERIFY_PASSES, WC_AUG_LAUNCHES, WC_N };
-
 constexpr int WIDE_PAR_GMAX = 64;      // most searches of one problem at once (cyto_lap_opts.wide_par)
 
 // The row caches of one problem against its prices v (lap_jv.hip: build_row_caches_wave, then replicate_group_caches over the runs of
@@ -28,7 +24,7 @@ struct WideJob {
     float *fws;                         // [6n + 16] v | u | - | cassign | label (2n)
     int32_t *iws;                       // [10n + 16] rowsol | colsol | matches | freerows | act0 | act1 | touched | slot_j | bid (2n)
     uint32_t *cache_col; float *cache_val;      // [n][64] row caches
-    char *misc;                         // 512 bytes (lap_wide.hip: WideArgs)
+    char *misc;                         // the status block (lap_dev.h: LapStatus)
     const int32_t *same;                // [n] 1 = the row equals the row before it (runs of identical rows), or null
     int ngroups;                        // runs of identical rows (n: none)
     DevBuf *state;                      // the solver's own state: allocated here

@@ -50,8 +50,7 @@ namespace cyto {
 //   act0, act1      [n] active-row lists of the row-reduction rounds;  freerows [n];  touched [n] columns labelled in a search
 //   slot_j, slot_p, slot_c  [n] per active slot: the bid's column (-1 = retired), price, raw cost of that entry
 //   cache_col/val   [n][64] row caches (lap_jv.hip: build_caches)
-//   misc            512 bytes: +4 status, +8 double total, +16 long long counters[] (lap_jv.hip indices), +160.. wide counters,
-//                   +256 phase timers ([12]: launches of wide_arr, [13] scaled?, [14] phases begun), +384 what the phase machine of the row reduction leaves for wide_arr
+//   misc            the status block (lap_dev.h: LapStatus)
 //   same_prev       [n] 1 = the row equals the row before it (runs of identical rows: CytoSPACE repeats a spot's row per slot), or null
 //   seg_sync        shared by the launch, or null: [0] workgroups that asked for fresh caches (zeroed by the driver before every launch
 //                   of wide_arr / wide_aug), [1 + b] wide_arr: 1 = problem b's rounds paused; wide_aug: searches problem b still has to run
@@ -61,7 +60,7 @@ namespace cyto {
 //   par_groups, par searches of one problem that run at once on as many workgroups (0 / 1: one at a time) and their state (ParCtl)
 //   arr_waste       wide_arr: full-row bids (with their cache refresh) of one launch after which the list rounds pause (aug_seg == 0)
 //   aug_seg         when a launch of wide_aug returns to the driver for fresh row caches: -1 never, k > 0 after k searches, 0 when
-//                   its full-row relaxations reach aug_waste or seg_quorum workgroups of the launch have asked (misc + 132 holds the
+//                   its full-row relaxations reach aug_waste or seg_quorum workgroups of the launch have asked (LapStatus::wide_done holds the
 //                   number of searches done)
 // (fields through an X-macro: the kernels read the block through a mirror struct whose pointers are typed as GLOBAL, so that
 //  every access is a global_* instruction -- through pointers loaded from memory it would be a FLAT one, and flat accesses
@@ -84,9 +83,6 @@ namespace {
 constexpr int WT = 1024;          // threads of the persistent workgroups: 16 waves
 constexpr int WNW = WT / 64;
 constexpr int RTB = 256;          // threads of the reduction-transfer workgroups
-
-// counters shared with lap_jv.hip (misc + 16, long long each)
-enum { C_RT = 0, C_ARR, C_AUG_INIT, C_AUG_RELAX, C_AUGS, C_HOPS, C_FREE_CR, C_FREE_A1, C_FREE_A2, C_ROWS_READ };
 
 template <typename T> __device__ __forceinline__ T ld_sc1(const T *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 template <typename T> __device__ __forceinline__ void st_sc1(T *p, T x) { __hip_atomic_store(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -277,7 +273,7 @@ __global__ __launch_bounds__(RTB) void wide_rt(const WideArgs *__restrict__ batc
     __syncthreads();
     for (int e = threadIdx.x; e < 256; e += RTB) if (s_hist[e]) atomicAdd(&sc->hist[e], s_hist[e]);
     if (threadIdx.x == 0 && s_vmax) atomicMax(&sc->vmaxbits, s_vmax);
-    if (lane == 0 && done) atomicAdd(reinterpret_cast<unsigned long long *>(a.misc + 16) + C_RT, (unsigned long long)done);
+    if (lane == 0 && done) atomicAdd(reinterpret_cast<unsigned long long *>(lap_status(a.misc)->counters) + C_RT, (unsigned long long)done);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -663,6 +659,8 @@ __device__ __forceinline__ unsigned long long bidkey(long long round, float pric
 __device__ __forceinline__ bool bid_won(unsigned long long word, int row) { return (int)((uint32_t)word & 0xFFFFFu) == row; }
 
 struct ArrHead { int cnt[2]; int started, free_cr; long long round, bids; int retired, dense; int done, launches; long long list_rounds; int no_more, pad_; };
+static_assert(sizeof(ArrHead) <= sizeof(LapStatus::arr), "ArrHead lives in LapStatus::arr");
+__device__ __forceinline__ ArrHead *arr_head(const WideArgs &a) { return reinterpret_cast<ArrHead *>(lap_status(a.misc)->arr); }
 
 // ---- the machine's memory beyond the driver's arrays (WideArgs.scx, wide_sc_ext_bytes(n) bytes, 256-byte aligned): the two buffers of
 // bid words (all-ones at the start: the first wide_sc_ones_bytes(n) bytes), the machine's two price arrays (ordered floats; wide_sc_init
@@ -972,7 +970,7 @@ __global__ __launch_bounds__(HEADB) void wide_sc_wipe(const WideArgs *__restrict
 __global__ void wide_sc_finish(const WideArgs *__restrict__ batch, int L) {
     const WideArgs a = load_wide_args(batch, blockIdx.x);
     ScCtl *sc = reinterpret_cast<ScCtl *>(a.sc);
-    ArrHead *h = reinterpret_cast<ArrHead *>(a.misc + 384);
+    ArrHead *h = arr_head(a);
     const ScSlot S = sc->slot[L & 1];
     const int na = sc->fin_cnt, want = (int)(S.total & 1);
     const bool chain = S.mode == SC_HANDOVER;
@@ -984,8 +982,8 @@ __global__ void wide_sc_finish(const WideArgs *__restrict__ batch, int L) {
     if (threadIdx.x == 0) {
         h->cnt[want] = na; h->cnt[want ^ 1] = 0; h->started = 1; h->free_cr = sc->free_cr; h->round = S.total; h->bids = S.bids;
         h->retired = sc->retired; h->dense = sc->dense; h->done = 0; h->launches = 0; h->list_rounds = S.total; h->no_more = chain ? 0 : 1;
-        long long *dbg = reinterpret_cast<long long *>(a.misc + 256);
-        dbg[13] = sc->phases > 0 ? 1 : 0; dbg[14] = sc->phases;
+        long long *tmr = lap_status(a.misc)->timers;
+        tmr[WT_SCALED] = sc->phases > 0 ? 1 : 0; tmr[WT_PHASES] = sc->phases;
     }
 }
 
@@ -1001,11 +999,11 @@ __global__ __launch_bounds__(WT) void wide_arr(const WideArgs *__restrict__ batc
     cx.s_cs = reinterpret_cast<uint16_t *>(cx.s_v + (VLDS ? ((n + 3) & ~3) : 0));
     cx.s = &s; cx.lane = lane;
     const long long t_kernel0 = wall_clock64();
-    // The rounds may take several launches (the control block at misc + 384 carries the state): like the searches of wide_aug, the
+    // The rounds may take several launches (LapStatus::arr carries the state): like the searches of wide_aug, the
     // list rounds return to the driver when the row caches have gone stale -- a row whose cache cannot certify its bid reads its
     // full row and rebuilds its own cache, three sweeps on one wave; once those have cost what a rebuild of ALL caches by the
     // whole chip costs (a.arr_waste of them in this launch; or a.seg_quorum workgroups of the launch have asked), that is cheaper.
-    ArrHead *h = reinterpret_cast<ArrHead *>(a.misc + 384);
+    ArrHead *h = arr_head(a);
     if (h->done) {                                               // finished in an earlier launch
         if (tid == 0 && a.seg_sync) a.seg_sync[1 + blockIdx.x] = a.seg_sync[1 + blockIdx.x] & 2;
         return;
@@ -1040,7 +1038,7 @@ __global__ __launch_bounds__(WT) void wide_arr(const WideArgs *__restrict__ batc
     __syncthreads();
     const int free_cr = headed ? h->free_cr : s.cnt[0];
     const long long t_start = wall_clock64();
-    if (tid == 0) reinterpret_cast<long long *>(a.misc + 256)[5] = t_start - t_kernel0;
+    if (tid == 0) lap_status(a.misc)->timers[WT_ARR_SETUP_TICKS] = t_start - t_kernel0;
     long long t_list = 0, t_chain = 0, n_list = 0, n_chain = 0, n_deal = 0;
     int32_t *A = cur ? a.act1 : a.act0, *B = cur ? a.act0 : a.act1;
     int na = free_cr;
@@ -1214,7 +1212,11 @@ __global__ __launch_bounds__(WT) void wide_arr(const WideArgs *__restrict__ batc
             }
         }
 #ifdef CYTO_WIDE_PROF
-        if (tid == 0) { long long *dbg = reinterpret_cast<long long *>(a.misc + 256); for (int k = 0; k < 5; k++) dbg[12 + k > 15 ? 15 : 12 + k] = tp[k]; dbg[7] = tp[4]; }
+        if (tid == 0) {     // the overlay (lap_dev.h, WT_*): the last of the five parts lands in WT_PAR_BATCHES and in WT_PAR_DISCARDED
+            long long *tmr = lap_status(a.misc)->timers;
+            for (int k = 0; k < 5; k++) tmr[WT_ARR_LAUNCHES + k > WT_PAR_BATCHES ? WT_PAR_BATCHES : WT_ARR_LAUNCHES + k] = tp[k];
+            tmr[WT_PAR_DISCARDED] = tp[4];
+        }
 #endif
     }
     __syncthreads();
@@ -1236,19 +1238,20 @@ __global__ __launch_bounds__(WT) void wide_arr(const WideArgs *__restrict__ batc
         __syncthreads();
     }
     if (tid == 0) {
-        long long *ctr = reinterpret_cast<long long *>(a.misc + 16);
-        long long *wc = reinterpret_cast<long long *>(a.misc + 160);
+        long long *ctr = lap_status(a.misc)->counters;
+        long long *wc = lap_status(a.misc)->wide;
         ctr[C_ARR] = bids; ctr[C_FREE_CR] = free_cr; ctr[C_FREE_A1] = numfree; ctr[C_FREE_A2] = numfree;
         wc[WC_ROUNDS] = round; wc[WC_BIDS] = bids; wc[WC_RETIRED] = s.retired; wc[WC_ACTIVE_LEFT] = left;
         wc[WC_FREE_ARR] = numfree; wc[WC_DENSE_ARR] = s.dense;
-        *reinterpret_cast<int *>(a.misc + 128) = numfree;
-        long long *dbg = reinterpret_cast<long long *>(a.misc + 256);      // (100 MHz ticks)
-        dbg[0] = n_list; dbg[1] += t_list; dbg[2] = n_chain; dbg[3] += t_chain; dbg[4] = n_deal; dbg[6] = wall_clock64() - t_tail0;
+        lap_status(a.misc)->numfree = numfree;
+        long long *tmr = lap_status(a.misc)->timers;
+        tmr[WT_LIST_ROUNDS] = n_list; tmr[WT_LIST_TICKS] += t_list; tmr[WT_CHAIN_ROUNDS] = n_chain; tmr[WT_CHAIN_TICKS] += t_chain;
+        tmr[WT_DEALS] = n_deal; tmr[WT_ARR_TAIL_TICKS] = wall_clock64() - t_tail0;
         // the state for the next launch, if the rounds paused (cur == round & 1: both flip together)
         h->started = 1; h->round = round; h->bids = bids; h->retired = s.retired; h->dense = s.dense; h->cnt[cur] = paused ? na : 0;
         h->cnt[cur ^ 1] = 0; h->free_cr = free_cr; h->done = paused ? 0 : 1; h->launches += 1; h->list_rounds = n_list;
 #ifndef CYTO_WIDE_PROF
-        dbg[12] = h->launches;
+        tmr[WT_ARR_LAUNCHES] = h->launches;
 #endif
         // bit 0: the rounds paused for fresh row caches; bit 1: the row reduction hardly ever had to read a full row (<= n / 64 bids):
         // the caches are evidently in good shape, the driver skips the rebuild before the searches (floors stay valid bounds while
@@ -1426,7 +1429,7 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
     uint32_t *dense = asg + nw32;
     float *s_v = reinterpret_cast<float *>(dense + nw32);
     uint16_t *s_cs = reinterpret_cast<uint16_t *>(s_v + (VLDS ? ((n + 3) & ~3) : 0));
-    const int numfree = *reinterpret_cast<const int *>(a.misc + 128);
+    const int numfree = lap_status(a.misc)->numfree;
     for (int b = tid; b < nblk; b += WT) bmin[b] = ~0ull;
     for (int q = tid; q < nw32; q += WT) { dirty[q] = 0; dense[q] = 0; }
     for (int c0 = 0; c0 < nw32 * 32; c0 += WT) {                 // assigned bits, 64 columns per wave and step
@@ -1439,16 +1442,16 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
             if (VLDS) s_v[j] = a.v[j];
             const int o = a.colsol[j]; s_cs[j] = o < 0 ? (uint16_t)0xFFFFu : (uint16_t)o;
         }
-    // The searches may take several launches, with the row caches rebuilt by the whole chip in between (misc + 132 = searches
+    // The searches may take several launches, with the row caches rebuilt by the whole chip in between (LapStatus::wide_done = searches
     // done so far).  A cache floor bounds c - v in absolute terms, as of the build; every search lowers the prices of the columns it
     // settles and raises their rows' duals with them, so after a few DEEP searches (few-cell-type chunks: a search settles most
     // columns) the floors lie below what the next search asks for and row after row falls back to its full cost row -- while
     // fresh caches certify practically everything (10 000-cell c4 chunk: 1.14 M full-row relaxations without a rebuild, 18 000
     // with one every 32 searches).  a.aug_seg: -1 never return early; k > 0 after k searches; 0: when the full-row relaxations of
     // this launch reach a.aug_waste (what a rebuild costs), or when a.seg_quorum workgroups of the launch have asked for one.
-    const int f0 = PAR ? 0 : *reinterpret_cast<const int *>(a.misc + 132);
+    const int f0 = PAR ? 0 : lap_status(a.misc)->wide_done;
     if (!PAR) {
-        long long *wc = reinterpret_cast<long long *>(a.misc + 160);
+        long long *wc = lap_status(a.misc)->wide;
         if (wc[WC_AUG_LAUNCHES] > 0 && f0 >= numfree) {          // finished in an earlier launch
             if (tid == 0 && a.seg_sync) a.seg_sync[1 + blockIdx.x] = 0;
             return;
@@ -2006,17 +2009,17 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
         double t = 0.0;
         for (int k = 0; k < WNW; k++) t += s_tot[k];
         const bool err = s.err || (PAR && (perr || ld_sc1(&pc->err)));
-        *reinterpret_cast<double *>(a.misc + 8) = t;
-        long long *ctr = reinterpret_cast<long long *>(a.misc + 16);
-        long long *wc = reinterpret_cast<long long *>(a.misc + 160);
+        LapStatus *st = lap_status(a.misc);
+        st->total = t;
+        long long *ctr = st->counters, *wc = st->wide;
         ctr[C_AUG_INIT] = numfree; ctr[C_AUG_RELAX] += c_relax; ctr[C_AUGS] = numfree; ctr[C_HOPS] += hops0;
         wc[WC_DENSE_AUG] += dn; wc[WC_AUG_LAUNCHES] += 1; wc[WC_AUG_ROUNDS] += c_rounds; wc[WC_AUG_PROCESSED] += proc; wc[WC_TRIVIAL] += triv; wc[WC_VERIFY_PASSES] += c_verify;
-        if (err) *reinterpret_cast<int *>(a.misc + 4) = 1;
-        *reinterpret_cast<int *>(a.misc + 132) = err ? numfree : f;      // searches done (an error ends them)
+        if (err) st->status = 1;
+        st->wide_done = err ? numfree : f;      // searches done (an error ends them)
         if (a.seg_sync) a.seg_sync[1 + (PAR ? 0 : blockIdx.x)] = err ? 0 : numfree - f;
-        long long *dbg = reinterpret_cast<long long *>(a.misc + 256);      // (100 MHz ticks)
-        dbg[8] += t_rounds; dbg[9] += t_verify; dbg[10] += t_finish; dbg[11] += t_triv;
-        if (PAR) { dbg[15] = ld_sc1(reinterpret_cast<unsigned long long *>(&pc->c_batches)); dbg[7] = ld_sc1(reinterpret_cast<unsigned long long *>(&pc->c_discarded)); }
+        long long *tmr = st->timers;
+        tmr[WT_AUG_ROUNDS_TICKS] += t_rounds; tmr[WT_AUG_VERIFY_TICKS] += t_verify; tmr[WT_AUG_FINISH_TICKS] += t_finish; tmr[WT_AUG_TRIVIAL_TICKS] += t_triv;
+        if (PAR) { tmr[WT_PAR_BATCHES] = ld_sc1(reinterpret_cast<unsigned long long *>(&pc->c_batches)); tmr[WT_PAR_DISCARDED] = ld_sc1(reinterpret_cast<unsigned long long *>(&pc->c_discarded)); }
     }
 }
 
@@ -2045,7 +2048,7 @@ __device__ __forceinline__ int nth_set(unsigned long long m, int k) {
 // column; 0: the cache does not certify the minimum, or nothing is free: the serial loop would stop here) and where it starts
 __global__ __launch_bounds__(HEADB) void wide_claim_lists(const WideArgs *__restrict__ batch) {
     const WideArgs a = load_wide_args(batch, blockIdx.y);
-    const int numfree = *reinterpret_cast<const int *>(a.misc + 128);
+    const int numfree = lap_status(a.misc)->numfree;
     const int lane = threadIdx.x & 63;
     const int gw = blockIdx.x * (HEADB / 64) + (threadIdx.x >> 6), nw = gridDim.x * (HEADB / 64);
     if (blockIdx.x == 0 && threadIdx.x == 0) { ClaimCtl *c = cl_ctl(a); c->changed = 0; c->blocked = 0x7FFFFFFF; c->rounds = 0; }
@@ -2082,7 +2085,7 @@ __global__ __launch_bounds__(HEADB) void wide_claim_lists(const WideArgs *__rest
 // a round: a thread per free row -- still holding its column?  else down the list to the next column no earlier row has
 __global__ __launch_bounds__(HEADB) void wide_claim_round(const WideArgs *__restrict__ batch) {
     const WideArgs a = load_wide_args(batch, blockIdx.y);
-    const int numfree = *reinterpret_cast<const int *>(a.misc + 128);
+    const int numfree = lap_status(a.misc)->numfree;
     int *claim = cl_claim(a);
     int changed = 0;
     for (int p = blockIdx.x * HEADB + threadIdx.x; p < numfree; p += gridDim.x * HEADB) {
@@ -2126,7 +2129,7 @@ __global__ void wide_claim_check(const WideArgs *__restrict__ batch, int nb, int
 // the fixed point: the first row that ran out of columns ...
 __global__ __launch_bounds__(HEADB) void wide_claim_blocked(const WideArgs *__restrict__ batch) {
     const WideArgs a = load_wide_args(batch, blockIdx.y);
-    const int numfree = *reinterpret_cast<const int *>(a.misc + 128);
+    const int numfree = lap_status(a.misc)->numfree;
     int first = 0x7FFFFFFF;
     for (int p = blockIdx.x * HEADB + threadIdx.x; p < numfree; p += gridDim.x * HEADB)
         if (cl_state(a)[p].y < 0) { first = p; break; }           // (positions ascend along a thread's stride: its first is its lowest)
@@ -2135,7 +2138,7 @@ __global__ __launch_bounds__(HEADB) void wide_claim_blocked(const WideArgs *__re
 // ... and the rows before it take their columns: the serial loop's assignments (no price changes; one hop each)
 __global__ __launch_bounds__(HEADB) void wide_claim_commit(const WideArgs *__restrict__ batch) {
     const WideArgs a = load_wide_args(batch, blockIdx.y);
-    const int numfree = *reinterpret_cast<const int *>(a.misc + 128);
+    const int numfree = lap_status(a.misc)->numfree;
     const int pb = min(cl_ctl(a)->blocked, numfree);
     for (int p = blockIdx.x * HEADB + threadIdx.x; p < pb; p += gridDim.x * HEADB) {
         const int fr = a.freerows[p], l = cl_state(a)[p].y;
@@ -2143,10 +2146,9 @@ __global__ __launch_bounds__(HEADB) void wide_claim_commit(const WideArgs *__res
         a.rowsol[fr] = c; a.colsol[c] = fr; a.cassign[c] = a.cache_val[(int64_t)fr * KC + l];
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        long long *ctr = reinterpret_cast<long long *>(a.misc + 16);
-        long long *wc = reinterpret_cast<long long *>(a.misc + 160);
-        ctr[C_HOPS] += pb; wc[WC_TRIVIAL] += pb;
-        *reinterpret_cast<int *>(a.misc + 132) = pb;             // wide_aug starts behind them
+        LapStatus *st = lap_status(a.misc);
+        st->counters[C_HOPS] += pb; st->wide[WC_TRIVIAL] += pb;
+        st->wide_done = pb;             // wide_aug starts behind them
     }
 }
 

@@ -439,6 +439,28 @@ def test_wide_several_searches_at_once(par):
     assert seen > 0
 
 
+@pytest.mark.parametrize("n,par", [(300, 0), (2500, 5)])
+def test_wide_launch_counts_and_phase_timers(n, par):
+    # what the wide kernels report beside the oracle's counters (launches, the split of the row-reduction rounds, the tick counts of
+    # their parts): every round is a list round or a chain round, a kernel that ran counts its launches, a part of a kernel takes
+    # no longer than the launches around it
+    c = np.random.default_rng(4000 + n).random((n, n)).astype(np.float32)
+    g, _ = _check_wide(c, opts=dict(wide_par=par))
+    i = g["info"]
+    d = i.as_dict()
+    print({k: d[k] for k in d if k.startswith("wide") or k in ("ms_arr", "ms_aug", "augmentations")})
+    assert i.wide_arr_launches >= 1
+    if i.augmentations > 0:
+        assert i.wide_aug_launches >= 1
+    assert i.wide_list_rounds >= 0 and i.wide_chain_rounds >= 0 and i.wide_list_rounds + i.wide_chain_rounds == i.wide_rounds
+    for k in ("wide_ms_list", "wide_ms_chain", "wide_ms_aug_rounds", "wide_ms_aug_verify", "wide_ms_aug_finish", "wide_ms_aug_trivial"):
+        assert np.isfinite(d[k]) and d[k] >= 0.0, (k, d[k])
+    assert i.wide_ms_list + i.wide_ms_chain <= i.ms_arr
+    assert i.wide_par_discarded >= 0
+    if par:
+        assert i.wide_par_batches >= 1
+
+
 def test_wide_single_solves_from_several_threads():
     # a single problem's searches run 16 at a time on 16 workgroups that wait for each other at grid barriers: only ONE such kernel may
     # be in flight per device (three of them could each get a part of their workgroups scheduled); a solve that finds the slot taken
