@@ -15,10 +15,10 @@ import numpy as np
 from . import _lib
 
 
-def lap_solve_rows(rows, rowmap, device_id=0, return_info=False, device_ptr=None, nu=None, ld=None, opts=None):
+def lap_solve_rows(rows, rowmap, device_id=0, return_info=False, device_ptr=None, nu=None, ld=None, opts=None, stream=None):
     """Solve the LAP whose row i is stored row rowmap[i] (C ABI: cyto_lap_f32_rowmap): `rows` holds every DISTINCT cost row
     once (nu x n, float32; or a device pointer with nu and ld), rowmap is what np.repeat(arange(nu), slots) gives.
-    Same result, bit for bit, as lap_solve(rows[rowmap])."""
+    Same result, bit for bit, as lap_solve(rows[rowmap]).  stream: a hipStream_t (int address) to launch on, as lap_solve's."""
     L = _lib.lib()
     rowmap = np.ascontiguousarray(rowmap, dtype=np.int32)
     n = len(rowmap)
@@ -38,7 +38,7 @@ def lap_solve_rows(rows, rowmap, device_id=0, return_info=False, device_ptr=None
     info = _lib.LapInfo()
     o = _lib.LapOpts(**opts) if opts else None
     st = L.cyto_lap_f32_rowmap(n, ptr, ld, int(nu), on_device, rowmap.ctypes.data, rowsol.ctypes.data, colsol.ctypes.data,
-                               u.ctypes.data, v.ctypes.data, ctypes.byref(total), ctypes.byref(info), device_id, None,
+                               u.ctypes.data, v.ctypes.data, ctypes.byref(total), ctypes.byref(info), device_id, stream,
                                ctypes.byref(o) if o is not None else None)
     _lib.check(st)
     out = dict(rowsol=rowsol, colsol=colsol, u=u, v=v, total=total.value)
@@ -47,13 +47,15 @@ def lap_solve_rows(rows, rowmap, device_id=0, return_info=False, device_ptr=None
     return out
 
 
-def lap_solve(cost, dtype=np.float32, device_id=0, return_info=False, device_ptr=None, n=None, ld=None, opts=None):
+def lap_solve(cost, dtype=np.float32, device_id=0, return_info=False, device_ptr=None, n=None, ld=None, opts=None, stream=None):
     """Solve a square LAP on the GPU.
 
     cost        2-D square array-like (host) -- cast to `dtype` -- or None with `device_ptr`
     device_ptr  int address of a device-resident row-major matrix (then give n and ld)
     opts        None, or a dict of cyto_lap_opts fields (chain_variant, augmentation, no_handover, inject_exceptions):
                 kernel selection only, the results never depend on it -- except certify / polish / exact (include/cytohip.h)
+    stream      None (the device's default stream), or a hipStream_t of the HIP runtime libcytohip.so uses, as an int address:
+                the solve is ordered behind what the caller queued there and complete on return (include/cytohip.h)
     Returns dict(rowsol, colsol, u, v, total[, info]).
     """
     L = _lib.lib()
@@ -91,14 +93,14 @@ def lap_solve(cost, dtype=np.float32, device_id=0, return_info=False, device_ptr
             ptr = c.ctypes.data
         fn = L.cyto_lap_f32_opts if dtype == np.float32 else L.cyto_lap_f64_opts
         st = fn(n, ptr, ld, on_device, rowsol.ctypes.data, colsol.ctypes.data, u.ctypes.data, v.ctypes.data,
-                ctypes.byref(total), ctypes.byref(info), device_id, None, ctypes.byref(o))
+                ctypes.byref(total), ctypes.byref(info), device_id, stream, ctypes.byref(o))
     elif narrow_on_device:
         st = L.cyto_lap_f32_from_f64(n, ptr, ld, rowsol.ctypes.data, colsol.ctypes.data, u.ctypes.data, v.ctypes.data,
-                                     ctypes.byref(total), ctypes.byref(info), device_id, None)
+                                     ctypes.byref(total), ctypes.byref(info), device_id, stream)
     else:
         fn = L.cyto_lap_f32 if dtype == np.float32 else L.cyto_lap_f64
         st = fn(n, ptr, ld, on_device, rowsol.ctypes.data, colsol.ctypes.data, u.ctypes.data, v.ctypes.data,
-                ctypes.byref(total), ctypes.byref(info), device_id, None)
+                ctypes.byref(total), ctypes.byref(info), device_id, stream)
     _lib.check(st)
     out = dict(rowsol=rowsol, colsol=colsol, u=u, v=v, total=total.value)
     if return_info:

@@ -54,6 +54,30 @@ int cyto_device_synchronize(int device_id);
  * chunks that run side by side).  This returns every cached block to the runtime. */
 int cyto_trim_device_cache(int device_id);
 
+/* ---- Device inputs and caller streams: what holds for every entry point below that takes a device matrix (cost_on_device,
+ * x_on_device, cyto_matrix.on_device) or a `void *stream` (tests/test_device_inputs_gpu.py, tests/test_caller_stream_gpu.py).
+ *
+ * Layout.  A device matrix is row-major with ANY leading dimension ld >= its width (elements) and ANY base address aligned to its
+ * element; the result does not depend on either, bit for bit.  Which layouts are read where they lie, without a copy:
+ *   cost (float32)        ld % 4 == 0 and a 16-byte aligned base;   cost (float64): ld % 2 == 0 and a 16-byte aligned base
+ *                         (anything else is re-pitched into a work buffer by one device-to-device copy: n x ld' more bytes)
+ *   cyto_transform / cyto_standardize / cyto_ctx_create_ex inputs: always in place.  The four-column kernels run when the width and
+ *                         ld are multiples of 4 and the base is aligned for four elements (16 bytes for float32 and float64, 8 for
+ *                         uint16, 4 for uint8) -- and z_dev is 16-byte aligned with ldz % 4 == 0; otherwise a column per lane
+ *   cyto_cost_metric / cyto_cost_pearson operands: in place; they keep their own rule (Gpad % 32 == 0, ld % 128 == 0, the columns
+ *                         between the width and the next multiple of 128 zero, as cyto_transform leaves them); cost_dev: any ldc >= C
+ * Padding.  Bytes outside the n x n (nu x n, G x C) block -- the columns between the width and ld, whatever lies before the base or
+ * behind the last row, stored rows no entry of a row map names -- are never interpreted: they may hold anything, NaN and infinities
+ * included, and do not raise CYTO_ERR_NONFINITE.  Inputs are never written.  Of an output the call writes its block and, for z_dev,
+ * the zero padding (the whole Gpad x ldz buffer outside the G x C block); nothing else, the columns between C and ldc of cost_dev
+ * included.
+ * Streams.  `stream` is a hipStream_t of the HIP runtime this library is linked against (NULL: the device's default stream).  All
+ * device work of the call is queued on it, behind whatever the caller queued there before: an input that an earlier copy or kernel on
+ * that stream is still producing is read when it is complete.  Every call returns with its work complete: host outputs are
+ * filled, device outputs (z_dev, cost_dev, dense_dev) may be read at once from any stream.
+ * Entry points WITHOUT a stream parameter (cyto_lap_batch_f32*, cyto_ctx_*, cyto_assign_*) run on private non-blocking streams, which
+ * wait for no other stream: their device inputs must be complete before the call. */
+
 /* ---- A5: the LAP solve.  Replaces `_, y, _ = lapjv.lapjv(cost_scaled)`
  * (cytospace/linear_assignment_solvers/linear_assignment_solvers.py:34-40; solver imported
  * at :16-18).  Jonker-Volgenant: column reduction, reduction transfer, two augmenting row

@@ -29,7 +29,9 @@ def _up(x, m):
 
 def _transform(x, transform, already, on_device):
     """cyto_transform into a z buffer pre-filled with 0xFF bytes (NaN).  Host input: ld = C (the 4-column kernels when C % 4 == 0).
-    Device input: a pitch ldx % 4 != 0 and a 1-element pointer offset (the 1-column kernels).  Returns the whole Gpad x ldz buffer."""
+    Device input: a pitch ldx % 4 != 0 and a 1-element pointer offset (the 1-column kernels), every element of the buffer that is not
+    data poisoned (NaN; the integer types: their maximum): nothing of it may reach a column sum, a moment or a rank.  Returns the
+    whole Gpad x ldz buffer."""
     L = _lib.lib()
     G, C = x.shape
     Gpad, ldz = _up(G, 32), _up(C, 128)
@@ -40,7 +42,7 @@ def _transform(x, transform, already, on_device):
             _lib.check(L.cyto_transform(transform, G, C, x.ctypes.data, C, dt, 0, already, z.ptr, ldz, Gpad, 0, None))
         else:
             ldx = C + 1 if (C + 1) % 4 else C + 2
-            host = np.zeros(G * ldx + 1, x.dtype)
+            host = np.full(G * ldx + 1, np.nan if x.dtype.kind == "f" else np.iinfo(x.dtype).max, x.dtype)
             host[1:].reshape(G, ldx)[:, :C] = x
             xd = _lib.DeviceBuffer.from_numpy(host)
             try:

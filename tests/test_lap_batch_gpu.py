@@ -291,22 +291,30 @@ def test_d_rejected_problems_leave_the_others_alone(n, bad, chain):
 # ---- (e) costs already on the device ----
 
 PAD = np.float32(-1e30)     # in every element of the buffer that is not a cost: a kernel that reads one changes the answer
+NAN_PAD = np.float32(np.nan)   # ... and what a recycled block may hold: a NaN taken for a cost also fails the solve (CYTO_ERR_NONFINITE)
 
 
 @pytest.mark.parametrize("chain", [False, True], ids=["wide", "chain"])
-@pytest.mark.parametrize("layout", ["in_place", "odd_pitch", "offset_base", "odd_pitch_and_offset_base"])
+@pytest.mark.parametrize("layout", ["in_place", "odd_pitch", "offset_base", "odd_pitch_and_offset_base",
+                                    "wide", "in_place_nan", "wide_nan", "odd_pitch_nan"])
 @pytest.mark.parametrize("n", [301, 1000])
 def test_e_costs_resident_on_the_device(n, layout, chain):
     # in_place: ld = n rounded up to 4 and a 16-byte aligned base, used where it lies; odd_pitch: ld = n + 1 (1000 -> 1001: rows not
     # 16-byte aligned); offset_base: the base 4 bytes into a larger allocation -- each of these goes through the device-to-device
-    # re-pitch of lap_solve_f32_batch
+    # re-pitch of lap_solve_f32_batch.  wide: ld = n rounded up to 4, plus 8 -- aligned, used in place, and wider than any padded
+    # width (a kernel that steps rows by (n + 3) & ~3 instead of ld reads the wrong rows).  *_nan: NaN instead of -1e30
     names = [_name(k, n) for k in (1, 2, 3, 5, 8)]
-    ld = n + 1 if "odd_pitch" in layout else (n + 3) // 4 * 4
+    pad = NAN_PAD if layout.endswith("_nan") else PAD
+    ld = n + 1 if "odd_pitch" in layout else (n + 3) // 4 * 4 + (8 if "wide" in layout else 0)
     lead = 1 if "offset_base" in layout else 0
     bufs = []
+
+    def is_pad(a):
+        return (a.view(np.uint32) == np.array([pad]).view(np.uint32)[0]).all()
+
     try:
         for nm in names:
-            h = np.full(lead + n * ld + 3, PAD, np.float32)
+            h = np.full(lead + n * ld + 3, pad, np.float32)
             h[lead:lead + n * ld].reshape(n, ld)[:, :n] = _cost(nm)
             bufs.append(_lib.DeviceBuffer.from_numpy(h))
         ptrs = [b.ptr + 4 * lead for b in bufs]
@@ -318,8 +326,8 @@ def test_e_costs_resident_on_the_device(n, layout, chain):
         for nm, buf in zip(names, bufs):
             back = buf.to_numpy((lead + n * ld + 3,), np.float32)
             assert np.array_equal(back[lead:lead + n * ld].reshape(n, ld)[:, :n], _cost(nm))
-            assert (back[:lead] == PAD).all() and (back[lead + n * ld:] == PAD).all()
-            assert (back[lead:lead + n * ld].reshape(n, ld)[:, n:] == PAD).all()
+            assert is_pad(back[:lead]) and is_pad(back[lead + n * ld:])
+            assert is_pad(np.ascontiguousarray(back[lead:lead + n * ld].reshape(n, ld)[:, n:]))
     finally:
         for b in bufs:
             b.free()
