@@ -124,6 +124,9 @@ def lib():
         L.cyto_lap_f32_rowmap.argtypes = [i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_double),
                                           ctypes.POINTER(LapInfo), i32, vp, ctypes.POINTER(LapOpts)]
         L.cyto_lap_f32_rowmap.restype = ctypes.c_int
+        if hasattr(L, "cyto_wide_embedded_solves"):          # (absent from older A/B builds loaded through CYTOHIP_LIB)
+            L.cyto_wide_embedded_solves.argtypes = []
+            L.cyto_wide_embedded_solves.restype = ctypes.c_longlong
         L.cyto_trim_device_cache.argtypes = [i32]
         L.cyto_trim_device_cache.restype = ctypes.c_int
         dp = ctypes.POINTER(ctypes.c_double)
@@ -219,6 +222,11 @@ def check(status):
     if status == 5:
         msg += ": " + L.cyto_last_hip_error().decode()
     raise _EXC.get(status, CytoHipError)(f"cytohip status {status}: {msg}")
+
+
+def wide_embedded_solves():
+    """Solves of this process whose searches ran in the wide solver's embedded form (cyto_wide_embedded_solves)."""
+    return int(lib().cyto_wide_embedded_solves())
 
 
 def device_count():

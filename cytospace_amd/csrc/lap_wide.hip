@@ -50,6 +50,9 @@ namespace cyto {
 //   act0, act1      [n] active-row lists of the row-reduction rounds;  freerows [n];  touched [n] columns labelled in a search
 //   slot_j, slot_p, slot_c  [n] per active slot: the bid's column (-1 = retired), price, raw cost of that entry
 //   cache_col/val   [n][64] row caches (lap_jv.hip: build_caches)
+//   cache_red       [n][64] the embedded searches' copy of the caches: fl(cache_val - v[cache_col]) per valid entry, kept current by the
+//                   commits; inv_off [n + 1], inv_ent: per column, the cache entries that hold it (bits of its raw cost << 32 |
+//                   row << 6 | slot), CSR.  Null where the embedded form cannot run
 //   misc            the status block (lap_dev.h: LapStatus)
 //   same_prev       [n] 1 = the row equals the row before it (runs of identical rows: CytoSPACE repeats a spot's row per slot), or null
 //   seg_sync        shared by the launch, or null: [0] workgroups that asked for fresh caches (zeroed by the driver before every launch
@@ -71,7 +74,7 @@ namespace cyto {
     P(int32_t, freerows) P(int32_t, act0) P(int32_t, act1) P(int32_t, touched) P(int32_t, slot_j) P(float, slot_p)            \
     P(float, slot_c) P(uint32_t, cache_col) P(float, cache_val) P(char, misc) S(long long, max_rounds)                     \
     P(const int32_t, same_prev) P(int32_t, seg_sync) S(int, aug_seg) S(int, aug_waste) S(int, arr_waste) S(int, seg_quorum)   \
-    P(char, sc) S(int, par_groups) P(char, par) P(char, scx)
+    P(char, sc) S(int, par_groups) P(char, par) P(char, scx) P(float, cache_red) P(const int32_t, inv_off) P(const unsigned long long, inv_ent)
 #define WIDE_F_PTR(T, name) T *name;
 #define WIDE_F_VAL(T, name) T name;
 struct WideArgs { WIDE_FIELDS(WIDE_F_PTR, WIDE_F_VAL) };
@@ -1318,7 +1321,8 @@ static_assert(WNW * 2 <= 32, "the queue of a round's full-row relaxations: two h
 //   after it, is discarded and runs again in the next batch.  Nothing of the restatement changes: same searches, same order, same bits.
 // Conflicts are found without a serial pass: every search claims its columns with an atomic max of (batch << 8 | 255 - g); after a
 // grid barrier a search whose columns all still carry its own key met no smaller g.  The committing workgroups log their price and
-// owner changes; every workgroup applies the log to its LDS copies before the next batch.  Grid barriers: three per batch.
+// owner changes; every workgroup applies the log to its LDS copies before the next batch.  Grid barriers: three per batch (the
+// embedded form, wide_aug<.., EMB>: four).
 struct ParCtl {
     unsigned int bar_arrive, bar_gen;
     int P[2], nplog[2], nolog[2];          // per batch parity: first conflicting search, entries of the two change logs
@@ -1397,9 +1401,48 @@ __device__ __forceinline__ void coop_dense_rows(AugShared *sp, int nd, const flo
     __syncthreads();                                                                // (the next round reads the block minima these set)
 }
 
-// VLDS: prices (f32) and column owners (u16) also in LDS (every update goes to both copies), as in wide_arr.
-template <bool VLDS, bool CLDS, bool PAR>
+// EMB (the embedded form: PAR without VLDS): a round of the other forms has a third dependent global round trip between its loads and its
+// offers -- the prices of the 2 x 63 cached columns, whose addresses come out of the cache rows.  The round uses a cached entry only as
+// fl(cache_val - v[col]), and prices change only at a commit, for the columns the committed search settled below its end: that difference
+// sits in cache_red and arrives with the cache row; behind a batch's commits the whole launch rewrites the entries of the columns the
+// price log names (embed_repair, through the inverse index), and meets at a fourth grid barrier.  Same two roundings in the same
+// order: same bits.  The certificate, the full-row paths and the price update read cache_val and v as before.
+// The repair: the entries of every column whose lane of `m` is set (column k, new price nv in that lane), a wave per column with
+// the lanes over its list.  Out of line: its registers must not weigh on the rounds.
+typedef __attribute__((address_space(1))) float gf32_t;
+typedef __attribute__((address_space(1))) const int32_t gci32_t;
+typedef __attribute__((address_space(1))) const unsigned long long gcu64_t;
+__device__ __noinline__ void embed_repair(gf32_t *cache_red, gci32_t *inv_off, gcu64_t *inv_ent, uint64_t m, int k, float nv) {
+    // (one column after the other was a chain of dependent round trips per column -- list bounds, entry, its cost, store: 2.5 ms at
+    //  50 000^2.  The bounds of all 64 columns are read at once, an entry carries its cost, and eight columns' lists are in flight.)
+    constexpr int U = 8;
+    const int lane = threadIdx.x & 63;
+    m = uni((unsigned long long)m);                                       // (an argument arrives in vector registers)
+    const bool mine = (m >> lane) & 1;
+    const int e0 = mine ? inv_off[k] : 0, e1 = mine ? inv_off[k + 1] : 0;
+    while (m) {
+        int b[U], e[U]; float x[U]; unsigned long long t[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const int l = m ? __ffsll((unsigned long long)m) - 1 : 0;
+            b[u] = m ? __builtin_amdgcn_readlane(e0, l) : 0;
+            e[u] = m ? __builtin_amdgcn_readlane(e1, l) : 0;
+            x[u] = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(nv), l));
+            m &= m - 1;
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) t[u] = b[u] + lane < e[u] ? inv_ent[b[u] + lane] : 0ull;
+#pragma unroll
+        for (int u = 0; u < U; u++) if (b[u] + lane < e[u]) cache_red[(uint32_t)t[u]] = __uint_as_float((uint32_t)(t[u] >> 32)) - x[u];
+#pragma unroll
+        for (int u = 0; u < U; u++)                                       // (lists longer than a wave: rare)
+            for (int p = b[u] + 64 + lane; p < e[u]; p += 64) { const unsigned long long y = inv_ent[p]; cache_red[(uint32_t)y] = __uint_as_float((uint32_t)(y >> 32)) - x[u]; }
+    }
+}
+
+template <bool VLDS, bool CLDS, bool PAR, bool EMB = false>
 __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batch) {
+    static_assert(!EMB || (PAR && !VLDS), "the embedded form: several searches at once, prices in global memory");
     extern __shared__ __align__(16) unsigned char w_smem[];
     __shared__ AugShared s;
     // (PAR: the launch has par_groups * stride workgroups of which every stride-th takes part: stride 1 = spread over all XCDs, 8 = one XCD)
@@ -1612,7 +1655,10 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
         if (w == 0) {
             const uint32_t col = a.cache_col[(int64_t)fr * KC + lane];
             const float val = a.cache_val[(int64_t)fr * KC + lane];
-            if (lane < KCU && col != COLSENT) relax_to((int)col, (unsigned long long)f2ord(val - getv((int)col)) << 12, fr);
+            if (EMB) {
+                const float red = ld_sc1(a.cache_red + (int64_t)fr * KC + lane);
+                if (lane < KCU && col != COLSENT) relax_to((int)col, (unsigned long long)f2ord(red) << 12, fr);
+            } else if (lane < KCU && col != COLSENT) relax_to((int)col, (unsigned long long)f2ord(val - getv((int)col)) << 12, fr);
         }
         __syncthreads();
 
@@ -1701,7 +1747,9 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
                 for (int q = 0; q < AP; q++) {
                     oi[q] = uni(oi_r[q]);
                     const int oix = oi[q] < 0 ? 0 : oi[q];
-                    col[q] = a.cache_col[(int64_t)oix * KC + lane]; val[q] = a.cache_val[(int64_t)oix * KC + lane];
+                    col[q] = a.cache_col[(int64_t)oix * KC + lane];
+                    // (EMB: the entry less its column's price, as of the last commit that changed it -- other workgroups write it between batches)
+                    val[q] = EMB ? ld_sc1(a.cache_red + (int64_t)oix * KC + lane) : a.cache_val[(int64_t)oix * KC + lane];
                 }
 #pragma unroll
                 for (int q = 0; q < AP; q++) {
@@ -1714,7 +1762,7 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
 #pragma unroll
                 for (int q = 0; q < AP; q++) {                       // (the cached columns' prices: LDS, or one more request for both)
                     const bool valid = lane < KCU && col[q] != COLSENT;
-                    vc[q] = getv(valid ? (int)col[q] : pjx[q]);
+                    vc[q] = EMB ? 0.0f : getv(valid ? (int)col[q] : pjx[q]);
                 }
 #pragma unroll
                 for (int q = 0; q < AP; q++) {
@@ -1724,7 +1772,7 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
                         c_proc++;
                         if ((dense[oi[q] >> 5] >> (oi[q] & 31)) & 1u) { dn[q] = true; continue; }
                         const float h = (ca[q] - vp[q]) - ord2f(dord);
-                        const unsigned long long lv = edge_lv(f2ord((val[q] - vc[q]) - h), dord, kq);
+                        const unsigned long long lv = edge_lv(f2ord(EMB ? val[q] - h : (val[q] - vc[q]) - h), dord, kq);
                         off[q] = lane < KCU && col[q] != COLSENT && (int)col[q] != pj[q] && lv <= Tlv;
                         co[q] = lv;
                     }
@@ -1962,6 +2010,19 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
             const int left = numfree - fbase;
             fbase += Pb < left ? Pb : left;                       // (Pb >= 1: the first search of a batch never conflicts)
             if (Pb < 1) perr = 1;
+            if (EMB) {
+                // the batch's price changes into cache_red, by every wave of every workgroup of the launch: eight log entries per wave
+                // and step, the lanes over the repriced columns' lists (embed_repair); then the launch meets once more
+                // (by the committing workgroup alone, before the third barrier: 64 scattered lines per store instruction from ONE CU,
+                //  and a deep search's columns on its 16 waves -- update + flip + reset 7.0 -> 7.9 ms at 50 000^2)
+                for (int e0 = (g * WNW + w) * 8; e0 < npl; e0 += G * WNW * 8) {
+                    const bool have_e = lane < 8 && e0 + lane < npl;
+                    const int k = have_e ? ld_sc1(plog_col + e0 + lane) : 0;
+                    const float nv = have_e ? ld_sc1(plog_val + e0 + lane) : 0.0f;
+                    embed_repair((gf32_t *)a.cache_red, (gci32_t *)a.inv_off, (gcu64_t *)a.inv_ent, __ballot(have_e), k, nv);
+                }
+                par_barrier(pc, G, pgen);
+            }
             batchno++; c_batches++;
         }
         AUG_LAP(t_finish)
@@ -2358,12 +2419,110 @@ static int wide_launch_arr(const WideArgs *d_args, int nb, int n, hipStream_t st
     return CYTO_OK;
 }
 
-static int wide_launch_aug(const WideArgs *d_args, int nb, int n, hipStream_t stream, int par_groups) {
-    const bool vlds = wide_aug_vlds(n), clds = wide_aug_clds(n);
+// ---- the embedded form's arrays, built by the whole chip between the last cache build and the searches ----
+// cache_red [n][KC] | inv_off [n + 1] | counts [n + 1] (the last word: the longest list) | block sums [2 x blocks] | rank [n][KC] | inv_ent [n * KCU]
+constexpr int EMB_GATE = 4 * KCU;       // longest inverse list the embedded form is launched with (a commit rewrites a list per repriced column)
+constexpr int EMB_SB = 256;             // columns per workgroup of the scan
+static size_t emb_a256(size_t b) { return (b + 255) / 256 * 256; }
+static int emb_blocks(int n) { return (n + EMB_SB - 1) / EMB_SB; }
+static size_t emb_off_cnt(int n) { return emb_a256((size_t)n * KC * 4) + emb_a256(((size_t)n + 1) * 4); }
+static size_t emb_off_bsum(int n) { return emb_off_cnt(n) + emb_a256(((size_t)n + 1) * 4); }
+static size_t emb_off_rank(int n) { return emb_off_bsum(n) + emb_a256((size_t)emb_blocks(n) * 8); }
+static size_t emb_off_ent(int n) { return emb_off_rank(n) + emb_a256((size_t)n * KC * 4); }
+static size_t wide_embed_bytes(int n) { return emb_off_ent(n) + emb_a256((size_t)n * KCU * 8); }
+// a wave per row: the entries less their columns' prices; every entry's rank in its column's list (which also counts the lists)
+__global__ __launch_bounds__(256) void embed_red_count(int n, const uint32_t *__restrict__ cache_col, const float *__restrict__ cache_val,
+                                                       const float *__restrict__ v, float *__restrict__ red, int32_t *__restrict__ cnt,
+                                                       int32_t *__restrict__ rank) {
+    const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n) return;
+    const uint32_t col = cache_col[(int64_t)i * KC + lane];
+    const float val = cache_val[(int64_t)i * KC + lane];
+    const bool valid = lane < KCU && col < (uint32_t)n;
+    red[(int64_t)i * KC + lane] = valid ? val - v[col] : 0.0f;
+    if (valid) rank[(int64_t)i * KC + lane] = atomicAdd(cnt + col, 1);
+}
+// EMB_SB columns per workgroup: their counts' sum and maximum
+__global__ __launch_bounds__(EMB_SB) void embed_block_sums(int n, const int32_t *__restrict__ cnt, int32_t *__restrict__ bsum) {
+    __shared__ int ws[EMB_SB / 64], wm[EMB_SB / 64];
+    const int j = blockIdx.x * EMB_SB + threadIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int c = j < n ? cnt[j] : 0, mx = c;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) { c += __shfl_xor(c, d); mx = max(mx, __shfl_xor(mx, d)); }
+    if (lane == 0) { ws[w] = c; wm[w] = mx; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t = 0, m = 0;
+        for (int k = 0; k < EMB_SB / 64; k++) { t += ws[k]; m = max(m, wm[k]); }
+        bsum[blockIdx.x] = t; bsum[gridDim.x + blockIdx.x] = m;
+    }
+}
+// list starts: the sums of the workgroups before this one (every workgroup adds them up for itself), then its own columns;
+// workgroup 0 also leaves the total in off[n] and the longest list in cnt[n]
+__global__ __launch_bounds__(EMB_SB) void embed_scan(int n, int32_t *__restrict__ cnt, const int32_t *__restrict__ bsum, int32_t *__restrict__ off) {
+    __shared__ int ws[EMB_SB / 64], wm[EMB_SB / 64], wt[EMB_SB / 64];
+    const int nb = gridDim.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    int before = 0, total = 0, mx = 0;
+    for (int k = tid; k < nb; k += EMB_SB) { const int t = bsum[k]; total += t; if (k < (int)blockIdx.x) before += t; mx = max(mx, bsum[nb + k]); }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) { before += __shfl_xor(before, d); total += __shfl_xor(total, d); mx = max(mx, __shfl_xor(mx, d)); }
+    if (lane == 0) { ws[w] = before; wt[w] = total; wm[w] = mx; }
+    const int j = blockIdx.x * EMB_SB + tid;
+    const int c = j < n ? cnt[j] : 0;
+    int inc = c;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(inc, d); if (lane >= d) inc += t; }
+    __shared__ int wi[EMB_SB / 64];
+    if (lane == 63) wi[w] = inc;
+    __syncthreads();
+    int base = 0, tot = 0, m = 0;
+    for (int k = 0; k < EMB_SB / 64; k++) { base += ws[k]; tot += wt[k]; m = max(m, wm[k]); if (k < w) base += wi[k]; }
+    if (j < n) off[j] = base + inc - c;
+    if (blockIdx.x == 0 && tid == 0) { off[n] = tot; cnt[n] = m; }
+}
+__global__ __launch_bounds__(256) void embed_fill(int n, const uint32_t *__restrict__ cache_col, const float *__restrict__ cache_val,
+                                                  const int32_t *__restrict__ off, const int32_t *__restrict__ rank, unsigned long long *__restrict__ ent) {
+    const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n) return;
+    const uint32_t col = cache_col[(int64_t)i * KC + lane];
+    const float val = cache_val[(int64_t)i * KC + lane];
+    if (lane < KCU && col < (uint32_t)n)
+        ent[off[col] + rank[(int64_t)i * KC + lane]] = ((unsigned long long)__float_as_uint(val) << 32) | ((uint32_t)i << 6) | (uint32_t)lane;
+}
+static int32_t *emb_counts(const WideArgs &wa, int n) { return reinterpret_cast<int32_t *>(reinterpret_cast<char *>(wa.cache_red) + emb_off_cnt(n)); }
+static int wide_build_embedded(const WideArgs &wa, int n, hipStream_t stream) {
+    char *eb = reinterpret_cast<char *>(wa.cache_red);
+    int32_t *cnt = emb_counts(wa, n), *bsum = reinterpret_cast<int32_t *>(eb + emb_off_bsum(n)), *rank = reinterpret_cast<int32_t *>(eb + emb_off_rank(n));
+    const int nb = emb_blocks(n);
+    CYTO_HIP(hipMemsetAsync(cnt, 0, ((size_t)n + 1) * 4, stream));
+    hipLaunchKernelGGL(embed_red_count, dim3((n + 3) / 4), dim3(256), 0, stream, n, wa.cache_col, wa.cache_val, wa.v, wa.cache_red, cnt, rank);
+    hipLaunchKernelGGL(embed_block_sums, dim3(nb), dim3(EMB_SB), 0, stream, n, cnt, bsum);
+    hipLaunchKernelGGL(embed_scan, dim3(nb), dim3(EMB_SB), 0, stream, n, cnt, bsum, const_cast<int32_t *>(wa.inv_off));
+    hipLaunchKernelGGL(embed_fill, dim3((n + 3) / 4), dim3(256), 0, stream, n, wa.cache_col, wa.cache_val, wa.inv_off, rank, const_cast<unsigned long long *>(wa.inv_ent));
+    CYTO_HIP(hipGetLastError());
+    return CYTO_OK;
+}
+static std::atomic<long long> g_embedded_solves{0};    // solves of this process whose searches ran in the embedded form
+
+// which of the searches' arrays live in LDS
+// (developer knob, read once per process: CYTO_AUG_LDS = 2 or unset: by size; 1: owners in LDS, prices global -- what n > ~24 000
+//  gets; 0: neither -- the n > 65 534 instantiation.  It only takes arrays OUT of LDS: same results, tools/wide_large.py)
+static void wide_aug_lds_choice(int n, bool &vlds, bool &clds) {
+    const int lds_knob = CYTO_KNOB("CYTO_AUG_LDS").set ? CYTO_KNOB("CYTO_AUG_LDS").value : 2;
+    vlds = lds_knob >= 2 && wide_aug_vlds(n); clds = lds_knob >= 1 && wide_aug_clds(n);
+}
+
+static int wide_launch_aug(const WideArgs *d_args, int nb, int n, hipStream_t stream, int par_groups, bool embed) {
+    bool vlds, clds;
+    wide_aug_lds_choice(n, vlds, clds);
     const size_t shm = wide_aug_lds_bytes(n, vlds, clds);
     if (shm > (size_t)LDS_DYNAMIC_MAX) return CYTO_ERR_UNSUPPORTED;
-    if (par_groups > 1) {                                          // one problem, several SEARCHES at once (blocks 0, 8, 16 ... take part)
+    if (par_groups > 1) {                                         // one problem, several SEARCHES at once (blocks 0, 8, 16 ... take part)
         void (*k)(const WideArgs *) = vlds ? wide_aug<true, true, true> : clds ? wide_aug<false, true, true> : wide_aug<false, false, true>;
+        if (embed) {
+            if (vlds) return CYTO_ERR_INTERNAL;
+            k = clds ? wide_aug<false, true, true, true> : wide_aug<false, false, true, true>;
+        }
         int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(k));
         if (rc) return rc;
         // (the searches' workgroups spread over all XCDs -- each with its own labels in its own L2 -- instead of packed on one: wide_aug 9.01 ->
@@ -2404,6 +2563,7 @@ int wide_solve_batch(const WidePlan &pl, const std::vector<WideJob> &jobs, hipSt
     (void)hipGetDevice(&dev_now);
     const int device_slot = dev_now >= 0 && dev_now < 64 ? dev_now : 0;
     const size_t nT = (size_t)n * sizeof(float);
+    const int embed_knob = CYTO_KNOB("CYTO_AUG_EMBED").set ? CYTO_KNOB("CYTO_AUG_EMBED").value : 1;
     std::vector<WideArgs> h_wa((size_t)nl);
     for (int k = 0; k < nl; k++) {
         const WideJob &j = jobs[(size_t)k];
@@ -2427,8 +2587,21 @@ int wide_solve_batch(const WidePlan &pl, const std::vector<WideJob> &jobs, hipSt
         const size_t sc_off = ((2 * nT + 255) / 256) * 256;            // the phase machine's control block behind everything else
         const size_t par_off = sc_off + WIDE_SC_BYTES;
         const size_t scx_off = ((par_off + parb + 255) / 256) * 256;     // the machine's own arrays (ScMem)
-        if ((rc = j.state->alloc(scx_off + wide_sc_ext_bytes(n), stream))) return rc;
+        // the embedded form of the searches (wide_aug<.., EMB>): several searches at once with the prices in global memory
+        // (developer knob, read once per process: CYTO_AUG_EMBED = 1 or unset: where the longest inverse list allows; 0: never; 2: always)
+        bool vlds_k, clds_k;
+        wide_aug_lds_choice(n, vlds_k, clds_k);
+        const bool emb_cand = parg > 1 && !vlds_k && n <= (1 << 25) && embed_knob != 0;
+        const size_t emb_off = ((scx_off + wide_sc_ext_bytes(n) + 255) / 256) * 256;
+        if ((rc = j.state->alloc(emb_cand ? emb_off + wide_embed_bytes(n) : scx_off + wide_sc_ext_bytes(n), stream))) return rc;
         WideArgs &wa = h_wa[(size_t)k];
+        wa.cache_red = nullptr; wa.inv_off = nullptr; wa.inv_ent = nullptr;
+        if (emb_cand) {
+            char *eb = j.state->as<char>() + emb_off;
+            wa.cache_red = reinterpret_cast<float *>(eb);
+            wa.inv_off = reinterpret_cast<int32_t *>(eb + emb_a256((size_t)n * KC * 4));
+            wa.inv_ent = reinterpret_cast<unsigned long long *>(eb + emb_off_ent(n));
+        }
         wa.n = n; wa.ld = j.ld; wa.cost = j.cost; wa.rowmap = j.rowmap;
         wa.v = j.fws; wa.u = j.fws + n; wa.cassign = j.fws + 3 * (int64_t)n;
         wa.label = reinterpret_cast<unsigned long long *>(j.fws + 4 * (int64_t)n);
@@ -2507,8 +2680,20 @@ int wide_solve_batch(const WidePlan &pl, const std::vector<WideJob> &jobs, hipSt
             for (int k = 0; k < nl; k++) dup = dup || h_wa[(size_t)k].same_prev != nullptr;
             if (dup && (rc = wide_launch_claims(d_wa.as<WideArgs>(), nl, n, stream, d_sync.as<int32_t>()))) return rc;
         }
+        bool embed = false;
+        if (parg > 0 && h_wa[0].cache_red) {                   // (one launch runs all searches: the caches are not rebuilt behind this)
+            if ((rc = wide_build_embedded(h_wa[0], n, stream))) return rc;
+            embed = embed_knob >= 2;
+            if (!embed) {                                      // the gate: a column in thousands of caches (few cell types) -- a deep search would rewrite most of the array
+                int32_t longest = 0;
+                CYTO_HIP(hipMemcpyAsync(&longest, emb_counts(h_wa[0], n) + n, sizeof longest, hipMemcpyDeviceToHost, stream));
+                CYTO_HIP(hipStreamSynchronize(stream));
+                embed = longest <= EMB_GATE;
+            }
+        }
         CYTO_HIP(hipMemsetAsync(d_sync.p, 0, sizeof(int32_t), stream));
-        if ((rc = wide_launch_aug(d_wa.as<WideArgs>(), nl, n, stream, parg))) return rc;
+        if ((rc = wide_launch_aug(d_wa.as<WideArgs>(), nl, n, stream, parg, embed))) return rc;
+        if (embed) g_embedded_solves.fetch_add(1);
         if (parg > 0) { CYTO_HIP(hipStreamSynchronize(stream)); break; }
         CYTO_HIP(hipMemcpyAsync(h_sync.data(), d_sync.p, sizeof(int32_t) * ((size_t)nl + 1), hipMemcpyDeviceToHost, stream));
         CYTO_HIP(hipStreamSynchronize(stream));                // (d_wa is read by the kernels until here)
@@ -2520,3 +2705,5 @@ int wide_solve_batch(const WidePlan &pl, const std::vector<WideJob> &jobs, hipSt
 }
 
 }  // namespace cyto
+
+extern "C" long long cyto_wide_embedded_solves(void) { return cyto::g_embedded_solves.load(); }

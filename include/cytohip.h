@@ -39,6 +39,9 @@ const char *cyto_version(void);
  * against another header version must compare these at load time (cytospace_amd/_lib.py does) instead of passing a struct
  * the library would overrun.  ABI history: INTEGRATION.md, "ABI versions". */
 int cyto_abi_sizes(size_t *lap_info, size_t *lap_opts, size_t *assign_info, size_t *chunk);
+/* Solves of this process whose searches ran in the wide solver's embedded form (one problem, several searches at once, prices in
+ * global memory: DESIGN 4.1a) -- a process-wide count, so that a test can tell which form ran; it is not part of cyto_lap_info. */
+long long cyto_wide_embedded_solves(void);
 
 /* ---- device + memory plumbing (so callers can keep the cost matrix resident in HBM) ---- */
 int cyto_device_count(int *count);

@@ -9,5 +9,5 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 name=$1; shift
 python -m cytospace_amd.build > /dev/null
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-result "$@" -c -o $R/cytospace_amd/build/lap_wide_$name.o $R/cytospace_amd/csrc/lap_wide.hip
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/cytospace_amd/build/libcytohip_$name.so $R/cytospace_amd/build/{core,lap_jv,cost,batch,comm}.o $R/cytospace_amd/build/lap_wide_$name.o -L/opt/rocm/lib -lrccl -lpthread
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/cytospace_amd/build/libcytohip_$name.so $R/cytospace_amd/build/{core,lap_jv,cost,batch,comm,downsample,table,mtx}.o $R/cytospace_amd/build/lap_wide_$name.o -L/opt/rocm/lib -lrccl -lpthread
 ls -la $R/cytospace_amd/build/libcytohip_$name.so
