@@ -124,7 +124,7 @@ int set_max_dynamic_lds(const void *kernel);
 int select_device(int device_id);
 int device_cus(int device_id);          // multiProcessorCount, queried once per device (256 if the query fails)
 
-// lap_jv.hip: float32 problems of ONE size solved as a batch (one launch per chain phase, a workgroup per problem)
+// lap_jv.hip (the float32 driver): float32 problems of ONE size solved as a batch (one launch per chain phase, a workgroup per problem)
 int lap_batch_same_n(int n, int nb, const float *const *cost, const int64_t *ld, int cost_on_device, int32_t *const *rowsol,
                      int32_t *const *colsol, float *const *u, float *const *v, double *total, cyto_lap_info *info, int *status,
                      int device_id, hipStream_t stream, const int32_t *const *rowmap = nullptr, const int *nu = nullptr,

@@ -1,4 +1,5 @@
-// lap_dev.h -- device helpers shared by the LAP kernels (lap_jv.hip: the chain solver; lap_wide.hip: the wide solver):
+// lap_dev.h -- device helpers shared by the LAP kernels (lap_jv.hip: the float32 chain solver; lap_f64.hip: the float64 solver;
+// lap_wide.hip: the wide solver; lap_exact.hip: the certificate and the exact option):
 // the status block of a solve (LapStatus) with its counter and timer indices, order-preserving float keys, DPP wave reductions, the
 // LDS-only barrier, the row-cache constants.
 #pragma once
@@ -27,7 +28,7 @@ enum { WT_LIST_ROUNDS = 0, WT_LIST_TICKS, WT_CHAIN_ROUNDS, WT_CHAIN_TICKS,      
        WT_N };
 
 // The status block of one float32 / float64 solve: device memory that the kernels of both solvers write and the host drivers
-// (lap_jv.hip) zero before the solve and read back after it.
+// (lap_jv.hip, lap_f64.hip) zero before the solve and read back after it.
 struct LapStatus {
     int nonfinite;                      // colred_partial: the cost holds a NaN or an infinity
     int status;                         // != 0: the solve failed (the finishers of the chain, the lazy and the wide kernels)

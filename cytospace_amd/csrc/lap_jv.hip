@@ -19,12 +19,16 @@
 //   jv_aug_lazy<LDS_STATE> (n > 5120) : AUGMENTATION with cache-certified scans and sparse search initialisation.
 //   jv_aug2<CH, LDS_STATE> (n <= 5120, and taking over from jv_aug_lazy on deep searches) : dense augmentation,
 //       per-column search state in registers.
-//   jv_chain<T, CH> : the generic dense chain (1024 threads) -- float64 only.
+// The float64 solver (jv_chain<T, CH>, jv_chain_stream) is lap_f64.hip, the float64 certificate and the exact option lap_exact.hip,
+// the wide solver -- what runs by default -- lap_wide.hip; this file also holds the float32 batch driver (lap_solve_f32_batch) that
+// all of them hang from, and the C entry points.
 //
 // Compile with -ffp-contract=off (build.py does): the arithmetic is subtract/compare only,
 // but nothing may be re-associated.
 #include "cyto_common.h"
 #include "lap_dev.h"
+#include "lap_chain.h"
+#include "lap_exact.h"
 #include "lap_wide.h"
 #include <math.h>
 #include <cmath>
@@ -34,112 +38,20 @@
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
-#include <atomic>
-#include <chrono>
-#include <functional>
 
 namespace cyto {
 
-constexpr int BLOCK = 1024;
-constexpr int NW = BLOCK / 64;
-
-template <typename T> struct VecOf;
-template <> struct VecOf<float> { using type = float4; static constexpr int W = 4; };
-template <> struct VecOf<double> { using type = double2; static constexpr int W = 2; };
-
-// Row indirection (first half): CytoSPACE repeats every spot row slots[s] times
-// (linear_assignment_solvers.py:63-66).  With a row map the cost holds every DISTINCT row once (S_u x C) and LAP row i reads
-// row rowmap[i]; without one (nullptr) row i is row i.  RBASE gives callees that compute `base + i * ld` themselves a base that
-// lands on the mapped row.
-__device__ __forceinline__ int64_t row_off(const int32_t *__restrict__ rowmap, int i, int64_t ld) {
-    return (int64_t)(rowmap ? rowmap[i] : i) * ld;
-}
-#define RBASE(cost_, rowmap_, i_, ld_) ((cost_) + (row_off((rowmap_), (i_), (ld_)) - (int64_t)(i_) * (ld_)))
-
-template <typename T> __device__ __forceinline__ T vec_get(const typename VecOf<T>::type &x, int e);
-template <> __device__ __forceinline__ float vec_get<float>(const float4 &x, int e) {
-    return e == 0 ? x.x : e == 1 ? x.y : e == 2 ? x.z : x.w;
-}
-template <> __device__ __forceinline__ double vec_get<double>(const double2 &x, int e) { return e == 0 ? x.x : x.y; }
-
-__device__ __forceinline__ bool memcmp_neq(float a, float b) { return __float_as_uint(a) != __float_as_uint(b); }
-__device__ __forceinline__ bool memcmp_neq(double a, double b) { return __double_as_longlong(a) != __double_as_longlong(b); }
-
-// ------------------------------------------------------------------------------------------
-// COLUMN REDUCTION
-// ------------------------------------------------------------------------------------------
-// Partial column minima over a block of rows.  Lane owns VW consecutive columns; each row is one
-// 16-byte load per lane (a wave reads 1 KiB contiguous).  Strict '<' while rows ascend keeps the
-// lowest row index on ties, exactly like the oracle's row-wise sweep.
-template <typename T>
-__global__ __launch_bounds__(256) void colred_partial(int n, int64_t ld, const T *__restrict__ cost,
-                                                      int rows_per_block, T *__restrict__ pmin,
-                                                      int32_t *__restrict__ parg, int *__restrict__ nonfinite,
-                                                      int nrows, const int32_t *__restrict__ ulist,
-                                                      const int32_t *__restrict__ ufirst) {
-    // nrows rows are swept (n without a row map).  With one: the k-th DISTINCT row that is in use is row ulist[k] of the
-    // cost and stands for the LAP rows starting at ufirst[k] (ascending in k) -- the lowest of them is what a tie keeps.
-    using V = typename VecOf<T>::type;
-    constexpr int VW = VecOf<T>::W;
-    const int q = blockIdx.x * 256 + threadIdx.x;  // vector-column index
-    const int col0 = q * VW;
-    const int r0 = blockIdx.y * rows_per_block;
-    const int r1 = min(nrows, r0 + rows_per_block);
-    if (col0 >= n) return;
-    T mn[VW];
-    int32_t arg[VW];
-    bool bad = false;
-#pragma unroll
-    for (int e = 0; e < VW; e++) { mn[e] = (T)INFINITY; arg[e] = ufirst ? ufirst[min(r0, nrows - 1)] : r0; }
-    const int64_t stride = ld / VW;
-#pragma unroll 4
-    for (int r = r0; r < r1; r++) {
-        const V x = *(reinterpret_cast<const V *>(cost + (int64_t)(ulist ? ulist[r] : r) * ld) + q);
-        const int32_t rid = ufirst ? ufirst[r] : r;
-#pragma unroll
-        for (int e = 0; e < VW; e++) {
-            const T xe = vec_get<T>(x, e);
-            if (col0 + e < n) bad |= !__builtin_isfinite(xe);
-            if (xe < mn[e]) { mn[e] = xe; arg[e] = rid; }
-        }
-    }
-    (void)stride;
-#pragma unroll
-    for (int e = 0; e < VW; e++) {
-        if (col0 + e < n) {
-            pmin[(int64_t)blockIdx.y * n + col0 + e] = mn[e];
-            parg[(int64_t)blockIdx.y * n + col0 + e] = arg[e];
-        }
-    }
-    if (bad) atomicOr(nonfinite, 1);
-}
-
-// Combine the row blocks in ascending order; v[j] = column minimum, imin[j] = its lowest row.
-// "Columns are claimed from the last to the first, the first claim of a row wins":
-// rowsol[i] = max{ j : imin[j] == i }, matches[i] = #{ j : imin[j] == i }.
-template <typename T>
-__global__ void colred_finish(int n, int nblocks, const T *__restrict__ pmin, const int32_t *__restrict__ parg,
-                              T *__restrict__ v, int32_t *__restrict__ imin, int32_t *rowsol, int32_t *matches) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    T mn = pmin[j];
-    int32_t arg = parg[j];
-    for (int b = 1; b < nblocks; b++) {
-        const T x = pmin[(int64_t)b * n + j];
-        if (x < mn) { mn = x; arg = parg[(int64_t)b * n + j]; }
-    }
-    v[j] = mn;
-    imin[j] = arg;
-    atomicMax(&rowsol[arg], j);
-    atomicAdd(&matches[arg], 1);
-}
-
+// COLUMN REDUCTION, the last step (colred_partial / colred_finish: lap_chain.h)
 __global__ void colred_assign(int n, const int32_t *__restrict__ imin, const int32_t *__restrict__ rowsol,
                               int32_t *__restrict__ colsol) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
     const int i = imin[j];
     colsol[j] = (rowsol[i] == j) ? i : -1;
+}
+
+void launch_colred_assign(int n, const int32_t *imin, const int32_t *rowsol, int32_t *colsol, hipStream_t stream) {
+    hipLaunchKernelGGL(colred_assign, dim3((n + 255) / 256), dim3(256), 0, stream, n, imin, rowsol, colsol);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -209,856 +121,10 @@ __global__ __launch_bounds__(1024) void rows_group_ids(int n, const int32_t *__r
     if (tid == 1023) *ngroups = s_part[1023];
 }
 
-// ------------------------------------------------------------------------------------------
-// Workgroup-wide reductions.  Values are reduced with wave64 shuffles, then the 16 wave
-// partials go through LDS once; every lane ends up with the result, so all threads can run
-// the (identical) scalar control logic without a broadcast.  `par` alternates 0/1 between
-// consecutive reductions so one barrier per reduction suffices.
-// ------------------------------------------------------------------------------------------
-template <typename T> struct Top2 {
-    T u1; uint32_t k1; T a1;  // lexicographic minimum (value, key) and an attached payload
-    T u2; uint32_t k2;        // lexicographic minimum excluding k1
-};
-
-template <typename T> __device__ __forceinline__ bool lex_less(T a, uint32_t ka, T b, uint32_t kb) {
-    return (a < b) || (a == b && ka < kb);
-}
-
-template <typename T> __device__ __forceinline__ void top2_push(Top2<T> &t, T h, uint32_t key, T aux) {
-    if (lex_less(h, key, t.u1, t.k1)) {
-        t.u2 = t.u1; t.k2 = t.k1;
-        t.u1 = h; t.k1 = key; t.a1 = aux;
-    } else if (lex_less(h, key, t.u2, t.k2)) {
-        t.u2 = h; t.k2 = key;
-    }
-}
-
-template <typename T> __device__ __forceinline__ void top2_merge(Top2<T> &a, const Top2<T> &b) {
-    if (lex_less(b.u1, b.k1, a.u1, a.k1)) {
-        T nu2; uint32_t nk2;
-        if (lex_less(a.u1, a.k1, b.u2, b.k2)) { nu2 = a.u1; nk2 = a.k1; } else { nu2 = b.u2; nk2 = b.k2; }
-        a.u1 = b.u1; a.k1 = b.k1; a.a1 = b.a1; a.u2 = nu2; a.k2 = nk2;
-    } else if (lex_less(b.u1, b.k1, a.u2, a.k2)) {
-        a.u2 = b.u1; a.k2 = b.k1;
-    }
-}
-
-template <typename T> struct RedScratch {
-    T u1[2][NW]; T a1[2][NW]; T u2[2][NW];
-    uint32_t k1[2][NW]; uint32_t k2[2][NW];
-    int scan[2][NW];
-};
-
-template <typename T> __device__ __forceinline__ Top2<T> top2_shfl_xor(const Top2<T> &t, int off) {
-    Top2<T> o;
-    o.u1 = __shfl_xor(t.u1, off); o.k1 = __shfl_xor(t.k1, off); o.a1 = __shfl_xor(t.a1, off);
-    o.u2 = __shfl_xor(t.u2, off); o.k2 = __shfl_xor(t.k2, off);
-    return o;
-}
-
-template <typename T> __device__ __forceinline__ Top2<T> wg_top2(Top2<T> t, RedScratch<T> &s, int &par) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) top2_merge(t, top2_shfl_xor(t, off));
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) { s.u1[par][w] = t.u1; s.k1[par][w] = t.k1; s.a1[par][w] = t.a1; s.u2[par][w] = t.u2; s.k2[par][w] = t.k2; }
-    __syncthreads();
-    const int l = lane & (NW - 1);
-    Top2<T> r;
-    r.u1 = s.u1[par][l]; r.k1 = s.k1[par][l]; r.a1 = s.a1[par][l]; r.u2 = s.u2[par][l]; r.k2 = s.k2[par][l];
-#pragma unroll
-    for (int off = NW / 2; off >= 1; off >>= 1) top2_merge(r, top2_shfl_xor(r, off));
-    par ^= 1;
-    return r;
-}
-
-// lexicographic (val, key) minimum with payload; cheaper than the full top-2
-template <typename T> struct Min1 { T u; uint32_t k; T a; };
-
-template <typename T> __device__ __forceinline__ Min1<T> wg_min1(Min1<T> t, RedScratch<T> &s, int &par) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const T ou = __shfl_xor(t.u, off); const uint32_t ok = __shfl_xor(t.k, off); const T oa = __shfl_xor(t.a, off);
-        if (lex_less(ou, ok, t.u, t.k)) { t.u = ou; t.k = ok; t.a = oa; }
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) { s.u1[par][w] = t.u; s.k1[par][w] = t.k; s.a1[par][w] = t.a; }
-    __syncthreads();
-    const int l = lane & (NW - 1);
-    Min1<T> r; r.u = s.u1[par][l]; r.k = s.k1[par][l]; r.a = s.a1[par][l];
-#pragma unroll
-    for (int off = NW / 2; off >= 1; off >>= 1) {
-        const T ou = __shfl_xor(r.u, off); const uint32_t ok = __shfl_xor(r.k, off); const T oa = __shfl_xor(r.a, off);
-        if (lex_less(ou, ok, r.u, r.k)) { r.u = ou; r.k = ok; r.a = oa; }
-    }
-    par ^= 1;
-    return r;
-}
-
-// exclusive prefix sum over the workgroup (thread order); returns offset, *total = sum
-template <typename T> __device__ __forceinline__ int wg_exscan(int x, RedScratch<T> &s, int &par, int *total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = x;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int y = __shfl_up(inc, off);
-        if (lane >= off) inc += y;
-    }
-    if (lane == 63) s.scan[par][w] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < NW; i++) {
-        const int c = s.scan[par][i];
-        if (i < w) base += c;
-        tot += c;
-    }
-    par ^= 1;
-    *total = tot;
-    return base + inc - x;
-}
-
-// ------------------------------------------------------------------------------------------
-// The sequential chain: REDUCTION TRANSFER -> AUGMENTING ROW REDUCTION x2 -> AUGMENTATION.
-// ------------------------------------------------------------------------------------------
-template <typename T> struct ChainArgs {
-    int n;
-    int64_t ld;
-    const T *cost;
-    T *v;                // [n] in: column minima; out: final prices
-    T *u;                // [n] out
-    int32_t *rowsol;     // [n] in/out
-    int32_t *colsol;     // [n] in/out
-    int32_t *matches;    // [n] in
-    int32_t *freerows;   // [n] scratch
-    int32_t *rtrows;     // [n] scratch
-    int32_t *pred;       // [n] scratch
-    double *total;       // [1] out
-    long long *counters; // [C_NCOUNTERS] out
-    int *status;         // [1] out (0 ok)
-    T *dwork;            // [n] scratch (jv_chain_stream: distances)
-    int32_t *lvl;        // [n] scratch (jv_chain_stream: level at which a column was scanned; 0 = not scanned)
-    const uint32_t *cache_col;   // [n x 64] jv_chain_stream: row caches (build_row_caches_wide), or nullptr
-    const T *cache_val;          // [n x 64]
-    int cs_lds;                  // jv_chain_stream: colsol as u16 in LDS during RT / ARR (n <= 65 535)
-    int v_lds;                   // jv_chain_stream: the prices in LDS too during RT / ARR (with cs_lds, where both fit)
-};
-
 // The persistent chain kernels run one workgroup per PROBLEM: a batch of independent chunk LAPs is one launch with
 // grid = batch size (consecutive workgroups land on consecutive XCDs, so the chains spread over the whole chip), each
 // workgroup reading its own argument block.  One stream per chunk instead tops out at ~32 concurrent kernels
 // (measured: 64 chunks on 64 streams took 3x as long as 32) and every 1-workgroup grid starts on XCD 0.
-
-// agent-scope relaxed accesses: served by L2, never by the scalar cache or a stale L1 line
-__device__ __forceinline__ int32_t ld_i32(const int32_t *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_i32(int32_t *p, int32_t x) {
-    __hip_atomic_store(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-template <typename T> __device__ __forceinline__ T ld_agent(const T *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-template <typename T, int CH, bool COLSOL_LDS>
-__global__ __launch_bounds__(BLOCK) void jv_chain(ChainArgs<T> a) {
-    using V = typename VecOf<T>::type;
-    constexpr int VW = VecOf<T>::W;
-    constexpr int NC = CH * VW;
-    static_assert(NC <= 64, "slot masks are 64-bit");
-    extern __shared__ __attribute__((aligned(16))) int32_t s_colsol[];
-    __shared__ RedScratch<T> red;
-
-    const int tid = threadIdx.x;
-    const int n = a.n;
-    const int64_t ld = a.ld;
-    const T *__restrict__ cost = a.cost;
-    int par = 0;
-    const T INF = (T)INFINITY;
-
-    // slot s = m*VW + e  <->  column (m*BLOCK + tid)*VW + e
-    auto slot_col = [&](int s) -> int { return ((s / VW) * BLOCK + tid) * VW + (s % VW); };
-    uint64_t validm = 0;
-#pragma unroll
-    for (int s = 0; s < NC; s++) if (slot_col(s) < n) validm |= (1ull << s);
-
-    auto colsol_get = [&](int j) -> int32_t { if constexpr (COLSOL_LDS) return s_colsol[j]; else return ld_i32(a.colsol + j); };
-    auto colsol_set = [&](int j, int32_t i) { if constexpr (COLSOL_LDS) s_colsol[j] = i; else st_i32(a.colsol + j, i); };
-
-    // ---- load prices and the assignment produced by the column reduction ----
-    T vreg[NC];
-    uint64_t assignedm = 0;
-#pragma unroll
-    for (int s = 0; s < NC; s++) {
-        const int c = slot_col(s);
-        vreg[s] = 0;
-        if (c < n) {
-            vreg[s] = a.v[c];
-            const int32_t cs = a.colsol[c];
-            if (cs >= 0) assignedm |= (1ull << s);
-            if constexpr (COLSOL_LDS) s_colsol[c] = cs;
-        }
-    }
-
-    auto load_row = [&](int i, V (&x)[CH]) {
-        const V *rp = reinterpret_cast<const V *>(cost + (int64_t)i * ld);
-#pragma unroll
-        for (int m = 0; m < CH; m++) {
-            const int q = m * BLOCK + tid;
-            if (q * VW < n) x[m] = rp[q];
-        }
-    };
-    // set vreg of column j (only its owner thread does anything)
-    auto set_v = [&](int j, T val) {
-        const int q = j / VW;
-        if ((q % BLOCK) == tid) {
-            const int s = (q / BLOCK) * VW + (j % VW);
-#pragma unroll
-            for (int t = 0; t < NC; t++) if (t == s) vreg[t] = val;
-        }
-    };
-    auto set_assigned = [&](int j) {
-        const int q = j / VW;
-        if ((q % BLOCK) == tid) assignedm |= (1ull << ((q / BLOCK) * VW + (j % VW)));
-    };
-
-    long long c_rt = 0, c_arr = 0, c_auginit = 0, c_augrelax = 0, c_augs = 0, c_hops = 0;
-    long long c_free_a1 = 0;
-
-    // ---- free-row list (matches == 0) and reduction-transfer list (matches == 1), ascending ----
-    int numfree = 0, nrt = 0;
-    {
-        const int R = (n + BLOCK - 1) / BLOCK;
-        const int r0 = min(n, tid * R), r1 = min(n, r0 + R);
-        int f = 0, g = 0;
-        for (int i = r0; i < r1; i++) { const int mt = a.matches[i]; f += (mt == 0); g += (mt == 1); }
-        int of = wg_exscan(f, red, par, &numfree);
-        int og = wg_exscan(g, red, par, &nrt);
-        for (int i = r0; i < r1; i++) {
-            const int mt = a.matches[i];
-            if (mt == 0) st_i32(a.freerows + of++, i);
-            else if (mt == 1) st_i32(a.rtrows + og++, i);
-        }
-    }
-    __syncthreads();
-    const long long c_free_cr = numfree;
-
-    // ---- REDUCTION TRANSFER ----
-    if (n > 1) {
-        for (int k = 0; k < nrt; k++) {
-            const int i = ld_i32(a.rtrows + k);
-            const int j1 = ld_i32(a.rowsol + i);
-            V x[CH];
-            load_row(i, x);
-            Min1<T> loc; loc.u = INF; loc.k = 0xFFFFFFFFu; loc.a = 0;
-#pragma unroll
-            for (int s = 0; s < NC; s++) {
-                const int c = slot_col(s);
-                if (((validm >> s) & 1) && c != j1) {
-                    const T h = vec_get<T>(x[s / VW], s % VW) - vreg[s];
-                    if (h < loc.u) loc.u = h;
-                }
-            }
-            loc.k = 0;  // value-only minimum
-            const Min1<T> g = wg_min1(loc, red, par);
-            // v[j1] = v[j1] - min  (owner only)
-            {
-                const int q = j1 / VW;
-                if ((q % BLOCK) == tid) {
-                    const int s = (q / BLOCK) * VW + (j1 % VW);
-#pragma unroll
-                    for (int t = 0; t < NC; t++) if (t == s) vreg[t] = vreg[t] - g.u;
-                }
-            }
-            c_rt++;
-        }
-    }
-
-    // ---- AUGMENTING ROW REDUCTION, two sweeps ----
-    const long long arr_budget = 1000ll * n + 1000000ll;   // == JV_ARR_BUDGET(n) of the oracle
-    for (int sweep = 0; sweep < 2; sweep++) {
-        int k = 0;
-        const int prev = numfree;
-        numfree = 0;
-        int carry = -1;
-        while (carry >= 0 || k < prev) {
-            if (c_arr >= arr_budget) {
-                // step budget exhausted (see oracle/jv_oracle_impl.h): hand the waiting rows to the
-                // augmentation phase, the displaced row first, then the rest in list order
-                if (carry >= 0) { if (tid == 0) st_i32(a.freerows + numfree, carry); numfree++; carry = -1; }
-                while (k < prev) { const int r = ld_i32(a.freerows + k); k++; if (tid == 0) st_i32(a.freerows + numfree, r); numfree++; }
-                break;
-            }
-            int i;
-            if (carry >= 0) { i = carry; carry = -1; }
-            else { i = ld_i32(a.freerows + k); k++; }
-            V x[CH];
-            load_row(i, x);
-            Top2<T> loc; loc.u1 = INF; loc.k1 = 0xFFFFFFFFu; loc.a1 = 0; loc.u2 = INF; loc.k2 = 0xFFFFFFFFu;
-#pragma unroll
-            for (int s = 0; s < NC; s++) {
-                if ((validm >> s) & 1) {
-                    const T h = vec_get<T>(x[s / VW], s % VW) - vreg[s];
-                    top2_push(loc, h, (uint32_t)slot_col(s), vreg[s]);
-                }
-            }
-            const Top2<T> g = wg_top2(loc, red, par);
-            c_arr++;
-            int j1 = (int)g.k1;
-            const int j2 = (int)g.k2;
-            int i0 = colsol_get(j1);
-            const T vj1 = g.a1;
-            const T vnew = vj1 - (g.u2 - g.u1);
-            const bool lowers = vnew < vj1;
-            if (lowers) set_v(j1, vnew);
-            else if (i0 >= 0) { j1 = j2; i0 = colsol_get(j2); }
-            __syncthreads();  // every wave has read colsol for this step before it changes
-            if (tid == 0) { st_i32(a.rowsol + i, j1); colsol_set(j1, i); }
-            set_assigned(j1);
-            if (i0 >= 0) {
-                if (lowers) carry = i0;
-                else { if (tid == 0) st_i32(a.freerows + numfree, i0); numfree++; }
-            }
-        }
-        __syncthreads();
-        if (sweep == 0) c_free_a1 = numfree;
-    }
-    const long long c_free_a2 = numfree;
-
-    // ---- AUGMENTATION ----
-    int err = 0;
-    for (int f = 0; f < numfree && !err; f++) {
-        const int freerow = ld_i32(a.freerows + f);
-        T dreg[NC];
-        uint64_t scannedm = 0, readym = 0;
-        {
-            V x[CH];
-            load_row(freerow, x);
-#pragma unroll
-            for (int s = 0; s < NC; s++) {
-                dreg[s] = INF;
-                if ((validm >> s) & 1) {
-                    dreg[s] = vec_get<T>(x[s / VW], s % VW) - vreg[s];
-                    a.pred[slot_col(s)] = freerow;
-                }
-            }
-            c_auginit++;
-        }
-        bool have = false;
-        T curmin = 0;
-        int endofpath = -1;
-        for (;;) {
-            // pick: lexicographic min of (d, assigned?, column) over unscanned columns
-            Min1<T> loc; loc.u = INF; loc.k = 0xFFFFFFFFu; loc.a = 0;
-#pragma unroll
-            for (int s = 0; s < NC; s++) {
-                if (((validm & ~scannedm) >> s) & 1) {
-                    const uint32_t key = (uint32_t)slot_col(s) | (((assignedm >> s) & 1) ? 0x80000000u : 0u);
-                    if (lex_less(dreg[s], key, loc.u, loc.k)) { loc.u = dreg[s]; loc.k = key; loc.a = vreg[s]; }
-                }
-            }
-            const Min1<T> g = wg_min1(loc, red, par);
-            if (g.k == 0xFFFFFFFFu) { err = CYTO_ERR_INTERNAL; break; }
-            const int jp = (int)(g.k & 0x7FFFFFFFu);
-            if (!have || g.u != curmin) { readym |= scannedm; curmin = g.u; have = true; }
-            if (!(g.k & 0x80000000u)) { endofpath = jp; break; }
-            // scan column jp through its row
-            {
-                const int q = jp / VW;
-                if ((q % BLOCK) == tid) scannedm |= (1ull << ((q / BLOCK) * VW + (jp % VW)));
-            }
-            const int i = colsol_get(jp);
-            const T cip = cost[(int64_t)i * ld + jp];
-            V x[CH];
-            load_row(i, x);
-            const T h = (cip - g.a) - curmin;
-#pragma unroll
-            for (int s = 0; s < NC; s++) {
-                if (((validm & ~scannedm) >> s) & 1) {
-                    const T v2 = (vec_get<T>(x[s / VW], s % VW) - vreg[s]) - h;
-                    if (v2 < dreg[s]) { dreg[s] = v2; a.pred[slot_col(s)] = i; }
-                }
-            }
-            c_augrelax++;
-        }
-        if (err) break;
-        // price update: columns scanned at an earlier level than the final one
-#pragma unroll
-        for (int s = 0; s < NC; s++)
-            if ((readym >> s) & 1) vreg[s] = (vreg[s] + dreg[s]) - curmin;
-        set_assigned(endofpath);
-        __syncthreads();  // pred stores of all waves are complete (and, via L2, visible)
-        if (tid == 0) {
-            int ep = endofpath, i;
-            do {
-                i = ld_i32(a.pred + ep);
-                colsol_set(ep, i);
-                const int j1 = ep;
-                ep = ld_i32(a.rowsol + i);
-                st_i32(a.rowsol + i, j1);
-                c_hops++;
-            } while (i != freerow);
-        }
-        c_augs++;
-        __syncthreads();
-    }
-
-    // ---- write back prices and colsol, then duals u and the total ----
-#pragma unroll
-    for (int s = 0; s < NC; s++) {
-        const int c = slot_col(s);
-        if (c < n) {
-            a.v[c] = vreg[s];
-            if constexpr (COLSOL_LDS) a.colsol[c] = s_colsol[c];
-        }
-    }
-    __threadfence_block();
-    __syncthreads();
-    double part = 0.0;
-    for (int i = tid; i < n; i += BLOCK) {
-        const int j = ld_i32(a.rowsol + i);
-        const T cij = cost[(int64_t)i * ld + j];
-        const T vj = __hip_atomic_load(a.v + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        a.u[i] = cij - vj;
-        part += (double)cij;
-    }
-    // deterministic tree sum
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off);
-    __shared__ double s_sum[NW];
-    if ((tid & 63) == 0) s_sum[tid >> 6] = part;
-    __syncthreads();
-    if (tid == 0) {
-        double t = 0.0;
-        for (int w = 0; w < NW; w++) t += s_sum[w];
-        *a.total = t;
-        a.counters[C_RT] = c_rt; a.counters[C_ARR] = c_arr; a.counters[C_AUG_INIT] = c_auginit;
-        a.counters[C_AUG_RELAX] = c_augrelax; a.counters[C_AUGS] = c_augs; a.counters[C_HOPS] = c_hops;
-        a.counters[C_FREE_CR] = c_free_cr; a.counters[C_FREE_A1] = c_free_a1; a.counters[C_FREE_A2] = c_free_a2;
-        a.counters[C_ROWS_READ] = c_rt + c_arr + c_auginit + c_augrelax;
-        *a.status = err;
-    }
-}
-
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t x);       // (defined with the float32 fast path below)
-__device__ __forceinline__ uint64_t wave_lexmin_u64(uint64_t k);
-
-// ------------------------------------------------------------------------------------------
-// Row caches for jv_chain_stream (the float64 chain beyond n = 4 096): the idea of the float32 fast path below -- prices
-// only decrease during REDUCTION TRANSFER and AUGMENTING ROW REDUCTION, so the (at most) 63 columns of a row with the
-// smallest reduced costs at build time, together with the 64th smallest reduced cost F (the floor), stay a certificate:
-// a later scan whose second-smallest recomputed cached value is < F has found the row's exact lexicographic top-2 --
-// in its simplest form.  One workgroup per row; the 64th smallest of the n order-preserving 64-bit keys is found bit by
-// bit (64 counting passes over the row, which stays in L2), then the columns below it are written in column order with
-// their raw costs.  Slot 63 holds the floor.
-// ------------------------------------------------------------------------------------------
-constexpr int WC_KC = 64;                          // slots per row; slot 63 = { sentinel, floor }
-constexpr uint32_t WC_SENT = 0xFFFFFFFFu;
-template <typename T> __device__ __forceinline__ uint64_t wide_ord(T h);
-template <> __device__ __forceinline__ uint64_t wide_ord<double>(double h) {
-    const uint64_t b = (uint64_t)__double_as_longlong(h + 0.0);
-    return b ^ ((uint64_t)((int64_t)b >> 63) | 0x8000000000000000ull);
-}
-template <> __device__ __forceinline__ uint64_t wide_ord<float>(float h) {
-    const uint32_t b = __float_as_uint(h + 0.0f);
-    return (uint64_t)(b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u)) << 32;
-}
-template <typename T>
-__global__ __launch_bounds__(256) void build_row_caches_wide(int n, int64_t ld, const T *__restrict__ cost, const T *__restrict__ v,
-                                                             uint32_t *__restrict__ cache_col, T *__restrict__ cache_val) {
-    __shared__ int s_cnt[2][4];
-    __shared__ int s_base;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int i = blockIdx.x;
-    const T *row = cost + (int64_t)i * ld;
-    uint64_t K = 0;
-    int par = 0;
-    if (n >= WC_KC) {
-        for (int b = 63; b >= 0; b--) {
-            const uint64_t cand = K | (1ull << b);
-            int c = 0;
-            for (int j = tid; j < n; j += 256) c += wide_ord<T>(row[j] - v[j]) < cand;
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off);
-            if (lane == 0) s_cnt[par][w] = c;
-            __syncthreads();
-            const int tot = s_cnt[par][0] + s_cnt[par][1] + s_cnt[par][2] + s_cnt[par][3];
-            par ^= 1;
-            if (tot < WC_KC) K = cand;             // fewer than 64 keys below cand: the 64th smallest is >= cand
-        }
-    } else K = ~0ull;                              // fewer than 64 columns: all of them are cached, the floor is +inf
-    // K is now the 64th smallest key: at most 63 keys are strictly below it, and its value is the floor
-    if (tid == 0) { s_base = 0; if (n < WC_KC) cache_val[(int64_t)i * WC_KC + WC_KC - 1] = (T)INFINITY; }
-    __syncthreads();
-    for (int j0 = 0; j0 < n; j0 += 256) {
-        const int j = j0 + tid;
-        const T c = j < n ? row[j] : (T)0;
-        const T h = j < n ? c - v[j] : (T)0;
-        const uint64_t key = j < n ? wide_ord<T>(h) : ~0ull;
-        const bool sel = j < n && key < K;
-        if (j < n && n >= WC_KC && key == K) cache_val[(int64_t)i * WC_KC + WC_KC - 1] = h;   // (equal keys = equal values)
-        const uint64_t m = __ballot(sel);
-        if (lane == 0) s_cnt[par][w] = __builtin_popcountll(m);
-        __syncthreads();
-        int off = s_base;
-        for (int ww = 0; ww < w; ww++) off += s_cnt[par][ww];
-        const int tot = s_cnt[par][0] + s_cnt[par][1] + s_cnt[par][2] + s_cnt[par][3];
-        if (sel) {
-            const int pos = off + __builtin_popcountll(m & ((1ull << lane) - 1));
-            cache_col[(int64_t)i * WC_KC + pos] = (uint32_t)j;
-            cache_val[(int64_t)i * WC_KC + pos] = c;
-        }
-        __syncthreads();
-        if (tid == 0) s_base = off + tot;          // (thread 0 is in wave 0: its off is the running base)
-        par ^= 1;
-        __syncthreads();
-    }
-    const int used = s_base;
-    for (int p = used + tid; p < WC_KC; p += 256) {
-        cache_col[(int64_t)i * WC_KC + p] = WC_SENT;
-        if (p < WC_KC - 1) cache_val[(int64_t)i * WC_KC + p] = (T)0;
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// The same chain with every per-column quantity (prices, distances, predecessors, scan levels) in L2-resident
-// global memory instead of VGPRs: jv_chain<double, CH> spills badly beyond CH = 2 (1024 threads leave 128 VGPRs
-// per lane), this variant has no per-lane arrays at all and takes any n.  Column c is only ever touched by thread
-// (c / VW) % BLOCK, so plain loads and stores in program order are all the ordering the per-column arrays need.
-// A row scan = one coalesced sweep of the cost row (HBM) and of the price vector (L2).  Same arithmetic, same
-// tie-breaking, same step budget as jv_chain / the oracle.
-// ------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(BLOCK) void jv_chain_stream(ChainArgs<T> a) {
-    using V = typename VecOf<T>::type;
-    constexpr int VW = VecOf<T>::W;
-    __shared__ RedScratch<T> red;
-    __shared__ int s_run[4];
-    __shared__ long long s_run_arr;
-    // with the row caches (n <= 65 535): colsol lives in LDS as u16 during REDUCTION TRANSFER / AUGMENTING ROW REDUCTION -- the cached
-    // step then gathers the owners from LDS and stores nothing but a lowered price to global memory (a load is only returned
-    // after the stores issued before it are acknowledged)
-    extern __shared__ __attribute__((aligned(16))) unsigned char dyn_cs[];
-    // ... and, where they fit beside it (a.v_lds: n <= ~15 800 in float64), the prices too: the cached step then touches global
-    // memory for the row's cache only
-    const bool vl = a.v_lds != 0;
-    T *const s_vT = reinterpret_cast<T *>(dyn_cs);
-    uint16_t *const s_cs16 = reinterpret_cast<uint16_t *>(dyn_cs + (vl ? (((size_t)a.n * sizeof(T) + 15) & ~(size_t)15) : 0));
-    const bool csl = a.cs_lds != 0;
-#define V_GET(j) (vl ? s_vT[j] : ld_agent(v + (j)))
-#define CS_GET(j) (csl ? (s_cs16[j] == 0xFFFFu ? -1 : (int32_t)s_cs16[j]) : ld_i32(a.colsol + (j)))
-    const int tid = threadIdx.x;
-    const int n = a.n;
-    const int64_t ld = a.ld;
-    const T *__restrict__ cost = a.cost;
-    T *v = a.v, *d = a.dwork;
-    int32_t *lvl = a.lvl, *pred = a.pred;
-    int par = 0;
-    const T INF = (T)INFINITY;
-    const int nq = (n + VW - 1) / VW;                  // vector chunks per row (rows and v are VW-aligned and padded)
-    const V *vp = reinterpret_cast<const V *>(v);
-
-    long long c_rt = 0, c_arr = 0, c_auginit = 0, c_augrelax = 0, c_augs = 0, c_hops = 0, c_free_a1 = 0, c_dense = 0;
-    const int lane = tid & 63;
-    int numfree = 0, nrt = 0;
-    {
-        const int R = (n + BLOCK - 1) / BLOCK;
-        const int r0 = min(n, tid * R), r1 = min(n, r0 + R);
-        int f = 0, g = 0;
-        for (int i = r0; i < r1; i++) { const int mt = a.matches[i]; f += (mt == 0); g += (mt == 1); }
-        int of = wg_exscan(f, red, par, &numfree);
-        int og = wg_exscan(g, red, par, &nrt);
-        for (int i = r0; i < r1; i++) {
-            const int mt = a.matches[i];
-            if (mt == 0) st_i32(a.freerows + of++, i);
-            else if (mt == 1) st_i32(a.rtrows + og++, i);
-        }
-    }
-    if (csl) for (int c = tid; c < n; c += BLOCK) { const int32_t r = a.colsol[c]; s_cs16[c] = r < 0 ? (uint16_t)0xFFFFu : (uint16_t)r; }
-    if (vl) for (int c = tid; c < n; c += BLOCK) s_vT[c] = v[c];
-    __syncthreads();
-    const long long c_free_cr = numfree;
-
-    // ---- REDUCTION TRANSFER ----
-    if (n > 1) {
-        for (int k = 0; k < nrt; k++) {
-            const int i = ld_i32(a.rtrows + k);
-            const int j1 = ld_i32(a.rowsol + i);
-            T mn = INF;
-            bool certified = false;
-            if (a.cache_col) {
-                // cached scan, by every wave for itself (same loads, same result: no exchange needed)
-                const uint32_t col = a.cache_col[(int64_t)i * WC_KC + lane];
-                const T cv = a.cache_val[(int64_t)i * WC_KC + lane];
-                const T F = __shfl(cv, WC_KC - 1);
-                T h = INF;
-                if (col != WC_SENT && (int)col != j1) h = cv - V_GET(col);
-#pragma unroll
-                for (int off = 32; off >= 1; off >>= 1) { const T o = __shfl_xor(h, off); h = o < h ? o : h; }
-                mn = h;
-                certified = mn < F;                    // every column outside the cache is still >= F
-            }
-            if (!certified) {
-                const V *rp = reinterpret_cast<const V *>(cost + (int64_t)i * ld);
-                Min1<T> loc; loc.u = INF; loc.k = 0; loc.a = 0;
-                for (int q = tid; q < nq; q += BLOCK) {
-                    const V x = rp[q], vv = vl ? reinterpret_cast<const V *>(s_vT)[q] : vp[q];
-#pragma unroll
-                    for (int e = 0; e < VW; e++) {
-                        const int c = q * VW + e;
-                        if (c < n && c != j1) { const T h = vec_get<T>(x, e) - vec_get<T>(vv, e); if (h < loc.u) loc.u = h; }
-                    }
-                }
-                mn = wg_min1(loc, red, par).u;
-                c_dense++;
-            }
-            if (((j1 / VW) % BLOCK) == tid) { if (vl) s_vT[j1] = s_vT[j1] - mn; else v[j1] = v[j1] - mn; }
-            if (a.cache_col) __syncthreads();          // the new price has reached L2 (the barrier waits for the store) before any wave gathers it
-            c_rt++;
-        }
-    }
-
-    // ---- AUGMENTING ROW REDUCTION, two sweeps ----
-    const long long arr_budget = 1000ll * n + 1000000ll;   // == JV_ARR_BUDGET(n) of the oracle
-    for (int sweep = 0; sweep < 2; sweep++) {
-        int k = 0;
-        const int prev = numfree;
-        numfree = 0;
-        int carry = -1;
-        while (carry >= 0 || k < prev) {
-            int pend = -1;
-            if (a.cache_col) {
-                // ---- wave 0 alone follows the displacement chains while the row caches certify its scans: no barrier, no
-                // other wave involved.  Lane = cache entry: the row's cache (requested as soon as the previous step knew the
-                // next row), one round of gathers (price and owner of every cached column), the top-2 by wave shuffles,
-                // the step's stores from lane 0 (agent scope: the wave's own later gathers see them, in L2).  It stops at the
-                // first row whose cache does not certify its top-2 (that row is then scanned by the whole workgroup, below),
-                // at the end of the sweep's list, or at the step budget. ----
-                if (tid < 64) {
-                    int pf_row = -1;
-                    uint32_t pf_col = WC_SENT;
-                    T pf_cv = 0;
-                    while ((carry >= 0 || k < prev) && c_arr < arr_budget) {
-                        const bool from_carry = carry >= 0;
-                        const int i = from_carry ? carry : ld_i32(a.freerows + k);
-                        uint32_t col; T cv;
-                        if (pf_row == i) { col = pf_col; cv = pf_cv; }
-                        else { col = ld_agent(a.cache_col + (int64_t)i * WC_KC + lane); cv = ld_agent(a.cache_val + (int64_t)i * WC_KC + lane); }
-                        const T F = __shfl(cv, WC_KC - 1);
-                        const bool valid = col != WC_SENT;
-                        const T vj = V_GET(valid ? col : 0u);
-                        const int32_t csj = CS_GET(valid ? col : 0u);
-                        // the smallest reduced cost and its lane (cache rows are sorted by column: the lowest lane is the lowest
-                        // column), then the smallest of the rest: reductions on order-preserving 64-bit keys, as in the float32 chain
-                        const T h = valid ? cv - vj : INF;
-                        const uint64_t kh = valid ? wide_ord<T>(h) : ~0ull;
-                        const uint64_t m1 = wave_lexmin_u64(kh);
-                        const int l1 = __builtin_ctzll(__ballot(kh == m1) | (1ull << 63));
-                        int i0 = __shfl(csj, l1);
-                        if (i0 >= 0 && m1 != ~0ull) {                         // (almost always) the next row of the chain: request its cache now
-                            pf_row = i0;
-                            pf_col = ld_agent(a.cache_col + (int64_t)i0 * WC_KC + lane);
-                            pf_cv = ld_agent(a.cache_val + (int64_t)i0 * WC_KC + lane);
-                        }
-                        const uint64_t kh2 = lane == l1 ? ~0ull : kh;
-                        const uint64_t m2 = wave_lexmin_u64(kh2);
-                        const int l2 = __builtin_ctzll(__ballot(kh2 == m2) | (1ull << 63));
-                        const T u1 = __shfl(h, l1), u2 = m2 == ~0ull ? INF : __shfl(h, l2);
-                        if (from_carry) carry = -1; else k++;                 // the row is taken, certified or not
-                        if (!(u2 < F)) { pend = i; break; }                   // (u2 < F: these are the row's exact lexicographic top-2)
-                        c_arr++;
-                        const int jfirst = (int)__shfl(col, l1);
-                        int j1 = jfirst;
-                        const int j2 = (int)__shfl(col, l2);
-                        const T vj1 = __shfl(vj, l1);
-                        const T vnew = vj1 - (u2 - u1);
-                        const bool lowers = vnew < vj1;
-                        if (!lowers && i0 >= 0) { j1 = j2; i0 = __shfl(csj, l2); }
-                        if (lane == 0) {
-                            if (lowers) { if (vl) s_vT[jfirst] = vnew; else __hip_atomic_store(v + jfirst, vnew, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-                            // (rowsol is not read during this phase and equals the inverse of colsol: rebuilt after it)
-                            if (csl) s_cs16[j1] = (uint16_t)i; else st_i32(a.colsol + j1, i);
-                            if (i0 >= 0 && !lowers) st_i32(a.freerows + numfree, i0);
-                        }
-                        if (i0 >= 0) { if (lowers) carry = i0; else numfree++; }
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");       // the stores have reached L2
-                    if (lane == 0) { s_run[0] = k; s_run[1] = carry; s_run[2] = numfree; s_run[3] = pend; s_run_arr = c_arr; }
-                }
-                __syncthreads();
-                k = s_run[0]; carry = s_run[1]; numfree = s_run[2]; pend = s_run[3]; c_arr = s_run_arr;
-                __syncthreads();                                             // (s_run is rewritten by the next run)
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");           // wave 0's prices: drop what this CU's L1 holds
-                if (pend < 0 && c_arr < arr_budget) continue;                // the sweep's list is exhausted
-            }
-            if (pend < 0 && c_arr >= arr_budget) {
-                if (carry >= 0) { if (tid == 0) st_i32(a.freerows + numfree, carry); numfree++; carry = -1; }
-                while (k < prev) { const int r = ld_i32(a.freerows + k); k++; if (tid == 0) st_i32(a.freerows + numfree, r); numfree++; }
-                break;
-            }
-            int i;
-            if (pend >= 0) i = pend;
-            else if (carry >= 0) { i = carry; carry = -1; }
-            else { i = ld_i32(a.freerows + k); k++; }
-            Top2<T> g;
-            const bool certified = false;
-            if (!certified) {
-                const V *rp = reinterpret_cast<const V *>(cost + (int64_t)i * ld);
-                Top2<T> loc; loc.u1 = INF; loc.k1 = 0xFFFFFFFFu; loc.a1 = 0; loc.u2 = INF; loc.k2 = 0xFFFFFFFFu;
-                for (int q = tid; q < nq; q += BLOCK) {
-                    const V x = rp[q], vv = vl ? reinterpret_cast<const V *>(s_vT)[q] : vp[q];
-#pragma unroll
-                    for (int e = 0; e < VW; e++) {
-                        const int c = q * VW + e;
-                        if (c < n) top2_push(loc, vec_get<T>(x, e) - vec_get<T>(vv, e), (uint32_t)c, vec_get<T>(vv, e));
-                    }
-                }
-                g = wg_top2(loc, red, par);
-                c_dense++;
-            }
-            c_arr++;
-            int j1 = (int)g.k1;
-            const int j2 = (int)g.k2;
-            int i0 = CS_GET(j1);
-            const T vj1 = g.a1;
-            const T vnew = vj1 - (g.u2 - g.u1);
-            const bool lowers = vnew < vj1;
-            if (lowers) { if (((j1 / VW) % BLOCK) == tid) { if (vl) s_vT[j1] = vnew; else v[j1] = vnew; } }
-            else if (i0 >= 0) { j1 = j2; i0 = CS_GET(j2); }
-            __syncthreads();  // every wave has read colsol for this step before it changes
-            if (tid == 0) { if (csl) s_cs16[j1] = (uint16_t)i; else st_i32(a.colsol + j1, i); }
-            if (i0 >= 0) {
-                if (lowers) carry = i0;
-                else { if (tid == 0) st_i32(a.freerows + numfree, i0); numfree++; }
-            }
-            __syncthreads();  // the colsol store is visible (L2) before the next step reads it
-        }
-        __syncthreads();
-        if (sweep == 0) c_free_a1 = numfree;
-    }
-    const long long c_free_a2 = numfree;
-    // colsol back to global memory, rowsol = its inverse (ARR kept only colsol current)
-    __syncthreads();
-    for (int c = tid; c < n; c += BLOCK) {
-        const int32_t r = CS_GET(c);
-        if (csl) a.colsol[c] = r;
-        if (vl) v[c] = s_vT[c];
-        if (r >= 0) a.rowsol[r] = c;
-    }
-    __threadfence();
-    __syncthreads();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#undef CS_GET
-#undef V_GET
-
-    // ---- AUGMENTATION: relaxation and the search for the next pick share one sweep ----
-    int err = 0;
-    for (int f = 0; f < numfree && !err; f++) {
-        const int freerow = ld_i32(a.freerows + f);
-        Min1<T> loc; loc.u = INF; loc.k = 0xFFFFFFFFu; loc.a = 0;
-        {
-            const V *rp = reinterpret_cast<const V *>(cost + (int64_t)freerow * ld);
-            for (int q = tid; q < nq; q += BLOCK) {
-                const V x = rp[q], vv = vp[q];
-#pragma unroll
-                for (int e = 0; e < VW; e++) {
-                    const int c = q * VW + e;
-                    if (c < n) {
-                        const T dd = vec_get<T>(x, e) - vec_get<T>(vv, e);
-                        d[c] = dd; pred[c] = freerow; lvl[c] = 0;
-                        const uint32_t key = (uint32_t)c | (ld_i32(a.colsol + c) >= 0 ? 0x80000000u : 0u);
-                        if (lex_less(dd, key, loc.u, loc.k)) { loc.u = dd; loc.k = key; loc.a = vec_get<T>(vv, e); }
-                    }
-                }
-            }
-            c_auginit++;
-        }
-        bool have = false;
-        T curmin = 0;
-        int endofpath = -1, level = 0;
-        for (;;) {
-            const Min1<T> g = wg_min1(loc, red, par);
-            if (g.k == 0xFFFFFFFFu) { err = CYTO_ERR_INTERNAL; break; }
-            const int jp = (int)(g.k & 0x7FFFFFFFu);
-            if (!have || g.u != curmin) { level++; curmin = g.u; have = true; }
-            if (!(g.k & 0x80000000u)) { endofpath = jp; break; }
-            if (((jp / VW) % BLOCK) == tid) lvl[jp] = level;                 // scanned (its d keeps the value at the pick)
-            const int i = ld_i32(a.colsol + jp);
-            const T cip = cost[(int64_t)i * ld + jp];
-            const T h = (cip - g.a) - curmin;
-            const V *rp = reinterpret_cast<const V *>(cost + (int64_t)i * ld);
-            loc.u = INF; loc.k = 0xFFFFFFFFu; loc.a = 0;
-            for (int q = tid; q < nq; q += BLOCK) {
-                const V x = rp[q], vv = vp[q];
-#pragma unroll
-                for (int e = 0; e < VW; e++) {
-                    const int c = q * VW + e;
-                    if (c < n && lvl[c] == 0) {
-                        const T v2 = (vec_get<T>(x, e) - vec_get<T>(vv, e)) - h;
-                        T dc = d[c];
-                        if (v2 < dc) { dc = v2; d[c] = v2; pred[c] = i; }
-                        const uint32_t key = (uint32_t)c | (ld_i32(a.colsol + c) >= 0 ? 0x80000000u : 0u);
-                        if (lex_less(dc, key, loc.u, loc.k)) { loc.u = dc; loc.k = key; loc.a = vec_get<T>(vv, e); }
-                    }
-                }
-            }
-            c_augrelax++;
-        }
-        if (err) break;
-        // price update: columns scanned at an earlier level than the final one
-        for (int q = tid; q < nq; q += BLOCK) {
-#pragma unroll
-            for (int e = 0; e < VW; e++) {
-                const int c = q * VW + e;
-                if (c < n) { const int lv = lvl[c]; if (lv != 0 && lv < level) v[c] = (v[c] + d[c]) - curmin; }
-            }
-        }
-        __threadfence_block();
-        __syncthreads();  // pred / price stores of all waves are complete (and, via L2, visible)
-        if (tid == 0) {
-            int ep = endofpath, i;
-            do {
-                i = ld_i32(pred + ep);
-                st_i32(a.colsol + ep, i);
-                const int j1 = ep;
-                ep = ld_i32(a.rowsol + i);
-                st_i32(a.rowsol + i, j1);
-                c_hops++;
-            } while (i != freerow);
-        }
-        c_augs++;
-        __syncthreads();
-    }
-
-    // ---- duals u and the total ----
-    __threadfence_block();
-    __syncthreads();
-    double part = 0.0;
-    if (!err) {
-        for (int i = tid; i < n; i += BLOCK) {
-            const int j = ld_i32(a.rowsol + i);
-            const T cij = cost[(int64_t)i * ld + j];
-            const T vj = __hip_atomic_load(a.v + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            a.u[i] = cij - vj;
-            part += (double)cij;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off);
-    __shared__ double s_sum[NW];
-    if ((tid & 63) == 0) s_sum[tid >> 6] = part;
-    __syncthreads();
-    if (tid == 0) {
-        double t = 0.0;
-        for (int w = 0; w < NW; w++) t += s_sum[w];
-        *a.total = t;
-        a.counters[C_RT] = c_rt; a.counters[C_ARR] = c_arr; a.counters[C_AUG_INIT] = c_auginit;
-        a.counters[C_AUG_RELAX] = c_augrelax; a.counters[C_AUGS] = c_augs; a.counters[C_HOPS] = c_hops;
-        a.counters[C_FREE_CR] = c_free_cr; a.counters[C_FREE_A1] = c_free_a1; a.counters[C_FREE_A2] = c_free_a2;
-        a.counters[C_ROWS_READ] = (a.cache_col ? c_dense : c_rt + c_arr) + c_auginit + c_augrelax;
-        *a.status = err;
-    }
-}
-
-
 
 // ==========================================================================================
 // float32 fast path ("v2").  Same arithmetic, same results, far fewer HBM row reads.
@@ -2481,7 +1547,6 @@ __global__ __launch_bounds__(BS) void jv_aug2(const Chain2Args *__restrict__ bat
 #undef SLOT_COL
 
 // ------------------------------------------------------------------------------------------
-constexpr int FAST_NMAX = 1 << 18;   // float32 cached-chain path (index arithmetic is 32-bit in bytes per row)
 __device__ __forceinline__ uint64_t ld_u64(const uint64_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_u64(uint64_t *p, uint64_t x) { __hip_atomic_store(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
@@ -2548,14 +1613,6 @@ __device__ __forceinline__ void lz_touch_blocks(bool act, int myblk, int myepoch
         ntouch++;
         todo &= ~__ballot(myblk == b);
     }
-}
-// lexicographic minimum of 64-bit keys over a wave as two 32-bit all-reduces (value, then the low word
-// among the lanes holding that value): much shorter dependency chains than a 64-bit DPP butterfly
-__device__ __forceinline__ uint64_t wave_lexmin_u64(uint64_t k) {
-    const uint32_t hi = (uint32_t)(k >> 32), lo = (uint32_t)k;
-    const uint32_t m = wave_min_u32(hi);
-    const uint32_t l = wave_min_u32(hi == m ? lo : 0xFFFFFFFFu);
-    return ((uint64_t)m << 32) | l;
 }
 // LDS_STATE: prices and colsol in LDS; CS_LDS (with !LDS_STATE, n <= 65535): colsol (u16) in LDS, prices in L2
 template <bool LDS_STATE, bool CS_LDS = false>
@@ -3099,173 +2156,10 @@ __global__ __launch_bounds__(BLOCK2) void jv_aug_lazy(const LazyArgs *__restrict
 }
 
 // ------------------------------------------------------------------------------------------
-// The float64 certificate of a float32 solve (cyto_lap_opts.certify).  The solvers compare fl32(c - v): an assigned row sits on a
-// minimum of its reduced costs AS ROUNDED, so in exact arithmetic its column can lose to another by a fraction of an ulp -- the
-// duals (u_i := c[i][rowsol_i] - v[rowsol_i], v) are feasible to ~1e-9, not exactly.  One more pass over the matrix turns that into a
-// PROOF of how far from optimal the assignment can be: with every difference evaluated in float64 (exact for float32 operands
-// whose exponents lie within 29 binades of each other),
-//     gap = sum_i ( u_i - min_j (c[i][j] - v[j]) )  >=  total - optimum  >=  0
-// (lower every u_i to its row's true minimum: the duals become feasible, their objective is total - gap).  gap == 0: the
-// assignment is optimal for the float32 matrix in exact arithmetic; an instance whose optimum is unique by more than `gap` has
-// exactly these indices whatever the solver's constants.  A wave per row, one sweep; the rows' terms are summed in row order
-// (one workgroup, fixed tree): the same bits on every run.
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void dual_gap_rows(int n, int64_t ld, const float *__restrict__ cost, const int32_t *__restrict__ rowmap,
-                                                     const int32_t *__restrict__ rowsol, const float *__restrict__ v,
-                                                     double *__restrict__ viol) {
-    const int lane = threadIdx.x & 63;
-    const int gw = blockIdx.x * 4 + (threadIdx.x >> 6), nw = gridDim.x * 4;
-    const int nq = (n + 3) >> 2;
-    const float4 *__restrict__ v4 = reinterpret_cast<const float4 *>(v);
-    for (int i = gw; i < n; i += nw) {
-        const float *__restrict__ row = cost + (int64_t)(rowmap ? rowmap[i] : i) * ld;
-        const float4 *__restrict__ r4 = reinterpret_cast<const float4 *>(row);
-        double m = INFINITY;
-        for (int q0 = lane; q0 < nq; q0 += 64 * 8) {
-            float4 x[8], p[8];
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const int q = q0 + 64 * k;
-                const bool in = q < nq && q * 4 + 3 < n;                 // (whole quads; the row's last, partial quad below)
-                x[k] = in ? r4[q] : make_float4(INFINITY, INFINITY, INFINITY, INFINITY);
-                p[k] = in ? v4[q] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            }
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                m = fmin(m, fmin(fmin((double)x[k].x - (double)p[k].x, (double)x[k].y - (double)p[k].y),
-                                 fmin((double)x[k].z - (double)p[k].z, (double)x[k].w - (double)p[k].w)));
-            }
-        }
-        if (lane < (n & 3)) { const int c = (n & ~3) + lane; m = fmin(m, (double)row[c] - (double)v[c]); }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) m = fmin(m, __shfl_xor(m, off));
-        if (lane == 0) {
-            const int j = rowsol[i];
-            const double ui = (double)row[j] - (double)v[j];
-            viol[i] = ui > m ? ui - m : 0.0;
-        }
-    }
-}
-// out[0] = sum (rows in ascending order within a thread, then a fixed tree), out[1] = max, out[2] = rows with a positive term
-__global__ __launch_bounds__(1024) void dual_gap_finish(int n, const double *__restrict__ viol, double *__restrict__ out) {
-    __shared__ double s_sum[1024], s_max[1024];
-    __shared__ int s_cnt[1024];
-    const int t = threadIdx.x;
-    const int per = (n + 1023) / 1024, lo = t * per, hi = min(n, lo + per);
-    double s = 0.0, mx = 0.0; int c = 0;
-    for (int i = lo; i < hi; i++) { const double x = viol[i]; s += x; mx = fmax(mx, x); c += x > 0.0; }
-    s_sum[t] = s; s_max[t] = mx; s_cnt[t] = c;
-    __syncthreads();
-    for (int w = 512; w > 0; w >>= 1) {
-        if (t < w) { s_sum[t] += s_sum[t + w]; s_max[t] = fmax(s_max[t], s_max[t + w]); s_cnt[t] += s_cnt[t + w]; }
-        __syncthreads();
-    }
-    if (t == 0) { out[0] = s_sum[0]; out[1] = s_max[0]; out[2] = (double)s_cnt[0]; }
-}
-
-// ------------------------------------------------------------------------------------------
-// The exact option (cyto_lap_opts.exact; DESIGN.md, "Exact option").  With pi = rowsol and, in float64 (exact as above),
-// w_ij = c_ij - v_j and r_ij = w_ij - w_i,pi(i): for any permutation sigma, cost(sigma) - cost(pi) = sum_i r_i,sigma(i), and
-// r_ij >= -s_i with gap = sum_i s_i (dual_gap_rows' terms).  An assignment that uses an edge with r > gap costs more than pi,
-// so the optimum lies in E = {(i, j) : r_ij <= tau}, tau = gap * (1 + 2^-30) (the slack covers the rounding of the n-term sum
-// and of each r; a larger tau only adds edges).  This pass emits E, the host finishes with a sparse solve over it.
-//
-// A wave per row (row t, or rows[t] of a list): c_i,pi and v_pi first, then one sweep selecting j != pi(i) with r_ij <= tau,
-// appended in column order (a ballot per bit of the lane's count, prefix popcounts) as (column, raw float32 cost) at
-// base = off ? off[t] : t * cap; the first `cap` are written, the true count and c_i,pi go to count / cpi (when given).  No atomics:
-// the same bytes on every run.  The float4 sweep only where the row and v are 16-byte aligned (any ld, any caller pointer: else
-// a column per lane).  Reads the gap dual_gap_finish left on the device; gap == 0 (nothing to repair): every wave returns at once.
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void near_tight_append(unsigned mask, int j0, const float (&xs)[4], int lane, int cap, int64_t base, int &cnt,
-                                                  int32_t *__restrict__ out_col, float *__restrict__ out_val) {
-    // mask: the lane's selections among columns j0 ... j0+3.  Three ballots (a lane selects at most 4) give every lane the number
-    // of selections in the lanes below it, and the wave's total
-    const int cl = __popc(mask);
-    const unsigned long long below = (1ull << lane) - 1ull;
-    int pre = 0, tot = 0;
-#pragma unroll
-    for (int b = 0; b < 3; b++) {
-        const unsigned long long m = __ballot((cl >> b) & 1);
-        pre += __popcll(m & below) << b;
-        tot += __popcll(m) << b;
-    }
-    int p = cnt + pre;
-#pragma unroll
-    for (int e = 0; e < 4; e++)
-        if ((mask >> e) & 1u) {
-            if (p < cap) { out_col[base + p] = j0 + e; out_val[base + p] = xs[e]; }
-            p++;
-        }
-    cnt += tot;
-}
-
-__global__ __launch_bounds__(256) void near_tight_rows(int nrows, int n, int64_t ld, const float *__restrict__ cost,
-                                                       const int32_t *__restrict__ rowmap, const int32_t *__restrict__ rowsol,
-                                                       const float *__restrict__ v, const double *__restrict__ gap,
-                                                       const int32_t *__restrict__ rows, const int64_t *__restrict__ off, int cap,
-                                                       int32_t *__restrict__ out_col, float *__restrict__ out_val,
-                                                       int32_t *__restrict__ count, float *__restrict__ cpi) {
-    const double g = *gap;
-    if (!(g > 0.0)) return;
-    const double tau = g * (1.0 + 0x1p-30);
-    const int lane = threadIdx.x & 63;
-    const int gw = blockIdx.x * 4 + (threadIdx.x >> 6), nw = gridDim.x * 4;
-    const int nq = n >> 2;                                           // whole quads; the last n & 3 columns after them
-    for (int t = gw; t < nrows; t += nw) {
-        const int i = rows ? rows[t] : t;
-        const float *__restrict__ row = cost + (int64_t)(rowmap ? rowmap[i] : i) * ld;
-        const int jp = rowsol[i];
-        const float cp = row[jp];
-        const double wp = (double)cp - (double)v[jp];
-        const int64_t base = off ? off[t] : (int64_t)t * cap;
-        int cnt = 0;                                                 // (wave-uniform)
-        const bool vec = ((reinterpret_cast<uintptr_t>(row) | reinterpret_cast<uintptr_t>(v)) & 15) == 0;
-        int done = 0;                                                // columns below `done` are swept
-        if (vec) {
-            const float4 *__restrict__ r4 = reinterpret_cast<const float4 *>(row);
-            const float4 *__restrict__ v4 = reinterpret_cast<const float4 *>(v);
-            for (int q0 = 0; q0 < nq; q0 += 64 * 8) {
-                float4 x[8], p[8];
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const int q = q0 + 64 * k + lane;
-                    const bool in = q < nq;
-                    x[k] = in ? r4[q] : make_float4(INFINITY, INFINITY, INFINITY, INFINITY);
-                    p[k] = in ? v4[q] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                }
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const int j0 = 4 * (q0 + 64 * k + lane);
-                    const float xs[4] = {x[k].x, x[k].y, x[k].z, x[k].w}, ps[4] = {p[k].x, p[k].y, p[k].z, p[k].w};
-                    unsigned mask = 0;
-#pragma unroll
-                    for (int e = 0; e < 4; e++)          // (padding lanes hold +inf: never selected)
-                        mask |= (unsigned)(j0 + e != jp && ((double)xs[e] - (double)ps[e]) - wp <= tau) << e;
-                    if (__ballot(mask != 0)) near_tight_append(mask, j0, xs, lane, cap, base, cnt, out_col, out_val);
-                }
-            }
-            done = nq * 4;
-        }
-        for (int c0 = done; c0 < n; c0 += 64) {                     // (a column per lane: the unaligned case, and the last n & 3 columns)
-            const int j = c0 + lane;
-            const float xs[4] = {j < n ? row[j] : INFINITY, 0.0f, 0.0f, 0.0f};
-            const unsigned mask = (j < n && j != jp && ((double)xs[0] - (double)v[j]) - wp <= tau) ? 1u : 0u;
-            if (__ballot(mask != 0)) near_tight_append(mask, j, xs, lane, cap, base, cnt, out_col, out_val);
-        }
-        if (lane == 0 && count) { count[i] = cnt; cpi[i] = cp; }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-static const cyto_lap_opts k_default_opts = {};
-// cyto_lap_opts.exact: edge slots per row of the first emission pass (exact = 1), the largest slot count a caller may ask for, and the cap
-// on E's edges beyond which the float64 polish runs instead (the host solve and its buffers stay a few hundred MB at most)
-constexpr int EXACT_SLOTS_DEFAULT = 16, EXACT_SLOTS_MAX = 64;
-static int64_t exact_edge_cap(int n) { return std::max<int64_t>((int64_t)1 << 22, (int64_t)32 * n); }
 
-static int check_opts(const cyto_lap_opts &o) {
+int check_opts(const cyto_lap_opts &o) {
     if (o.chain_variant < 0 || o.chain_variant > 3 || o.augmentation < 0 || o.augmentation > 2 || o.inject_exceptions < 0 ||
         o.no_handover < 0 || o.no_handover > 1)
         return CYTO_ERR_BAD_ARG;
@@ -3278,89 +2172,6 @@ static int check_opts(const cyto_lap_opts &o) {
     if (o.certify < 0 || o.certify > 1 || o.polish < 0 || o.polish > 1) return CYTO_ERR_BAD_ARG;
     if (o.exact < 0 || o.exact > EXACT_SLOTS_MAX || (o.exact && o.polish)) return CYTO_ERR_BAD_ARG;
     for (int r : o.reserved) if (r != 0) return CYTO_ERR_BAD_ARG;            // (must be zero: room for later knobs without another ABI break)
-    return CYTO_OK;
-}
-
-// ---- the host half of the exact option (cyto_lap_repair_sparse): successive shortest paths over a sparse E ----
-// Rows whose own edge is not their cheapest are freed; u_i = min_j r_ij, v = 0 are then feasible and tight on the rows kept (the JV
-// invariant: an assigned row sits on a minimum of r_ij - v_j), so each free row in ascending order runs one Dijkstra over the
-// columns with those potentials -- a binary heap keyed on (distance, column), equal distances to the lower column -- up to the first
-// unassigned column it settles; the settled columns' prices drop by (their distance - the path's), the path is flipped.  What
-// comes out is an optimum of the sparse problem; rows off every augmenting path keep their column.  *nfree / *changed: may be null.
-static int repair_sparse(int n, const int32_t *rowsol, const int64_t *rp, const int32_t *cols, const double *r, int32_t *out,
-                         int64_t *nfree, int64_t *changed) {
-    if (n <= 0 || !rowsol || !rp || !cols || !r || !out || rp[0] != 0) return CYTO_ERR_BAD_ARG;
-    std::vector<int32_t> rs((size_t)n), cs((size_t)n, -1);
-    std::vector<double> ra((size_t)n), v((size_t)n, 0.0);     // ra[i]: r of row i's assigned edge
-    std::vector<int32_t> freerows;
-    std::vector<char> seen((size_t)n, 0);
-    for (int i = 0; i < n; i++) {
-        const int j0 = rowsol[i];
-        if (j0 < 0 || j0 >= n || seen[(size_t)j0] || rp[i + 1] < rp[i]) return CYTO_ERR_BAD_ARG;
-        seen[(size_t)j0] = 1;
-        double mn = INFINITY, own = INFINITY;
-        for (int64_t e = rp[i]; e < rp[i + 1]; e++) {
-            const int j = cols[e];
-            if (j < 0 || j >= n || !std::isfinite(r[e])) return CYTO_ERR_BAD_ARG;
-            mn = std::min(mn, r[e]);
-            if (j == j0) own = std::min(own, r[e]);
-        }
-        if (own == INFINITY) return CYTO_ERR_BAD_ARG;        // (the starting assignment must lie in E)
-        rs[(size_t)i] = j0;
-        if (mn < own) { freerows.push_back(i); rs[(size_t)i] = -1; }
-        else { cs[(size_t)j0] = i; ra[(size_t)i] = own; }
-    }
-    // per search: distances and predecessors of the columns it touched (stamped, so nothing is cleared between searches)
-    std::vector<double> d((size_t)n), pr((size_t)n);
-    std::vector<int32_t> pred((size_t)n), stamp((size_t)n, -1), settled_at((size_t)n, -1);
-    std::vector<int32_t> settled;
-    typedef std::pair<double, int32_t> Key;
-    std::vector<Key> heap;
-    auto push = [&](double dist, int32_t j) { heap.emplace_back(dist, j); std::push_heap(heap.begin(), heap.end(), std::greater<Key>()); };
-    for (int s = 0; s < (int)freerows.size(); s++) {
-        const int f = freerows[(size_t)s];
-        heap.clear(); settled.clear();
-        auto relax = [&](int i, double base) {               // base: distance of row i's entry minus its own reduced cost
-            for (int64_t e = rp[i]; e < rp[i + 1]; e++) {
-                const int k = cols[e];
-                if (settled_at[(size_t)k] == s) continue;
-                const double nd = base + (r[e] - v[(size_t)k]);
-                if (stamp[(size_t)k] != s || nd < d[(size_t)k]) {
-                    stamp[(size_t)k] = s; d[(size_t)k] = nd; pred[(size_t)k] = i; pr[(size_t)k] = r[e];
-                    push(nd, k);
-                }
-            }
-        };
-        relax(f, 0.0);
-        int end = -1;
-        double D = 0.0;
-        while (!heap.empty()) {
-            std::pop_heap(heap.begin(), heap.end(), std::greater<Key>());
-            const Key top = heap.back();
-            heap.pop_back();
-            const int j = top.second;
-            if (settled_at[(size_t)j] == s || top.first != d[(size_t)j]) continue;       // (stale entry)
-            settled_at[(size_t)j] = s;
-            settled.push_back(j);
-            const int i = cs[(size_t)j];
-            if (i < 0) { end = j; D = top.first; break; }
-            relax(i, top.first - (ra[(size_t)i] - v[(size_t)j]));
-        }
-        if (end < 0) return CYTO_ERR_INTERNAL;             // (no augmenting path: E held no perfect matching)
-        for (int j : settled) v[(size_t)j] += d[(size_t)j] - D;
-        for (int j = end;;) {                               // flip the path
-            const int i = pred[(size_t)j];
-            const int k = rs[(size_t)i];
-            cs[(size_t)j] = i; rs[(size_t)i] = j; ra[(size_t)i] = pr[(size_t)j];
-            if (i == f) break;
-            j = k;
-        }
-    }
-    int64_t ch = 0;
-    for (int i = 0; i < n; i++) { ch += rs[(size_t)i] != rowsol[i]; }
-    for (int i = 0; i < n; i++) out[i] = rs[(size_t)i];
-    if (nfree) *nfree = (int64_t)freerows.size();
-    if (changed) *changed = ch;
     return CYTO_OK;
 }
 
@@ -3502,162 +2313,8 @@ static int launch_batch(const F32Plan &pl, std::vector<F32Job> &jobs, hipStream_
     return CYTO_OK;
 }
 
-// ---- the exact option around the certificate (cyto_lap_opts.exact) ----
-static int lap_polish_f64(int n, const float *cost, int64_t ld, int cost_on_device, const int32_t *rowmap_host, int nu, const float *v32,
-                          int32_t *rowsol, int32_t *colsol, float *u, float *v, double *total, double *ms_out, int device_id,
-                          hipStream_t stream);
-struct ExactRun {
-    int64_t status = 0, edges = 0, free_rows = 0, changed = 0, overflow = 0;   // (cyto_lap_info.exact_*)
-    double ms_emit = 0.0, ms_repair = 0.0;
-    int cap = 0;
-    const double *d_gap = nullptr;          // the certificate's sum on the device (alive while the certificate's buffer is)
-    DevBuf b_slots;                         // column (n x cap) | cost (n x cap) | count (n) | c_i,pi (n)
-    Events<4> ev;
-    std::vector<float> v;                   // the float32 prices: the polish's start when E is over its cap
-};
-
-// the first emission pass, queued behind dual_gap_finish (d_gap: the sum it leaves on the device)
-static int exact_emit(ExactRun &ex, int n, int cap, const F32Job &j, const double *d_gap, int grid, hipStream_t stream) {
-    int rc;
-    ex.cap = cap; ex.d_gap = d_gap;
-    if ((rc = ex.ev.create())) return rc;
-    const size_t nk = (size_t)n * cap;
-    if ((rc = ex.b_slots.alloc(nk * 8 + (size_t)n * 8, stream))) return rc;
-    int32_t *s_col = ex.b_slots.as<int32_t>();
-    float *s_val = reinterpret_cast<float *>(s_col + nk);
-    int32_t *cnt = reinterpret_cast<int32_t *>(s_val + nk);
-    float *cpi = reinterpret_cast<float *>(cnt + n);
-    CYTO_HIP(hipEventRecord(ex.ev[0], stream));
-    hipLaunchKernelGGL(near_tight_rows, dim3(grid), dim3(256), 0, stream, n, n, j.dld, j.dcost, j.rowmap(), j.b_iws.as<int32_t>(),
-                       j.b_fws.as<float>(), d_gap, (const int32_t *)nullptr, (const int64_t *)nullptr, cap, s_col, s_val, cnt, cpi);
-    CYTO_HIP(hipGetLastError());
-    CYTO_HIP(hipEventRecord(ex.ev[1], stream));
-    return CYTO_OK;
-}
-
-// after the certificate has arrived: the overflow pass, E on the host, the sparse solve, the repaired result back into the device
-// buffers the results are read from (rowsol | colsol, u, total) -- or, over the cap, status 3 (the caller polishes)
-static int exact_repair(ExactRun &ex, int n, F32Job &j, double gap, int grid, hipStream_t stream) {
-    int rc;
-    if (!(gap > 0.0)) {                                      // (the emission returned at once)
-        ex.status = 1;
-        float ms = 0.0f;
-        (void)hipEventElapsedTime(&ms, ex.ev[0], ex.ev[1]);
-        ex.ms_emit = ms;
-        return CYTO_OK;
-    }
-    const int cap = ex.cap;
-    const size_t nk = (size_t)n * cap, nI = (size_t)n * sizeof(int32_t);
-    int32_t *s_col = ex.b_slots.as<int32_t>();
-    float *s_val = reinterpret_cast<float *>(s_col + nk);
-    int32_t *d_cnt = reinterpret_cast<int32_t *>(s_val + nk);
-    float *d_cpi = reinterpret_cast<float *>(d_cnt + n);
-    int32_t *d_rowsol = j.b_iws.as<int32_t>();
-    float *d_v = j.b_fws.as<float>();
-    std::vector<int32_t> cnt((size_t)n), pi((size_t)n);
-    std::vector<float> cpi((size_t)n);
-    ex.v.resize((size_t)n);
-    CYTO_HIP(hipMemcpyAsync(cnt.data(), d_cnt, nI, hipMemcpyDeviceToHost, stream));
-    CYTO_HIP(hipMemcpyAsync(cpi.data(), d_cpi, nI, hipMemcpyDeviceToHost, stream));
-    CYTO_HIP(hipMemcpyAsync(pi.data(), d_rowsol, nI, hipMemcpyDeviceToHost, stream));
-    CYTO_HIP(hipMemcpyAsync(ex.v.data(), d_v, nI, hipMemcpyDeviceToHost, stream));
-    CYTO_HIP(hipStreamSynchronize(stream));
-    std::vector<int32_t> over_rows;
-    std::vector<int64_t> over_off;
-    int64_t over_total = 0;
-    for (int i = 0; i < n; i++) {
-        ex.edges += cnt[(size_t)i];
-        if (cnt[(size_t)i] > cap) { over_rows.push_back(i); over_off.push_back(over_total); over_total += cnt[(size_t)i]; }
-    }
-    ex.overflow = (int64_t)over_rows.size();
-    float ms1 = 0.0f, ms2 = 0.0f;
-    (void)hipEventElapsedTime(&ms1, ex.ev[0], ex.ev[1]);
-    if (ex.edges > exact_edge_cap(n)) { ex.status = 3; ex.ms_emit = ms1; return CYTO_OK; }
-    // rows over their slots: emitted again, exactly, into a list of their own
-    DevBuf b_list, b_csr;
-    std::vector<int32_t> o_col((size_t)over_total);
-    std::vector<float> o_val((size_t)over_total);
-    if (!over_rows.empty()) {
-        const size_t m = over_rows.size();
-        if ((rc = b_list.alloc(m * 12 + 16, stream)) || (rc = b_csr.alloc((size_t)over_total * 8, stream))) return rc;
-        int64_t *d_off = b_list.as<int64_t>();
-        int32_t *d_rows = reinterpret_cast<int32_t *>(d_off + m);
-        CYTO_HIP(hipMemcpyAsync(d_off, over_off.data(), m * 8, hipMemcpyHostToDevice, stream));
-        CYTO_HIP(hipMemcpyAsync(d_rows, over_rows.data(), m * 4, hipMemcpyHostToDevice, stream));
-        int32_t *c_col = b_csr.as<int32_t>();
-        float *c_val = reinterpret_cast<float *>(c_col + over_total);
-        CYTO_HIP(hipEventRecord(ex.ev[2], stream));
-        hipLaunchKernelGGL(near_tight_rows, dim3(std::max(1, std::min(grid, (int)((m + 3) / 4)))), dim3(256), 0, stream, (int)m, n, j.dld, j.dcost,
-                           j.rowmap(), d_rowsol, d_v, ex.d_gap, d_rows, d_off, INT32_MAX, c_col, c_val, (int32_t *)nullptr, (float *)nullptr);
-        CYTO_HIP(hipGetLastError());
-        CYTO_HIP(hipEventRecord(ex.ev[3], stream));
-        CYTO_HIP(hipMemcpyAsync(o_col.data(), c_col, (size_t)over_total * 4, hipMemcpyDeviceToHost, stream));
-        CYTO_HIP(hipMemcpyAsync(o_val.data(), c_val, (size_t)over_total * 4, hipMemcpyDeviceToHost, stream));
-    }
-    std::vector<int32_t> h_col(nk);
-    std::vector<float> h_val(nk);
-    CYTO_HIP(hipMemcpyAsync(h_col.data(), s_col, nk * 4, hipMemcpyDeviceToHost, stream));
-    CYTO_HIP(hipMemcpyAsync(h_val.data(), s_val, nk * 4, hipMemcpyDeviceToHost, stream));
-    CYTO_HIP(hipStreamSynchronize(stream));
-    if (!over_rows.empty()) (void)hipEventElapsedTime(&ms2, ex.ev[2], ex.ev[3]);
-    ex.ms_emit = (double)ms1 + ms2;
-
-    // E in CSR: per row the assignment's own edge (r = 0) first, then the emitted ones, r recomputed with the kernel's operations
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<int64_t> rp((size_t)n + 1);
-    std::vector<int32_t> ecol((size_t)(n + ex.edges));
-    std::vector<double> er((size_t)(n + ex.edges));
-    std::vector<float> ecost((size_t)(n + ex.edges));
-    int64_t e = 0;
-    for (int i = 0, o = 0; i < n; i++) {
-        rp[(size_t)i] = e;
-        const int jp = pi[(size_t)i];
-        const double wp = (double)cpi[(size_t)i] - (double)ex.v[(size_t)jp];
-        ecol[(size_t)e] = jp; er[(size_t)e] = 0.0; ecost[(size_t)e] = cpi[(size_t)i]; e++;
-        const int c = cnt[(size_t)i];
-        const bool ov = c > cap;
-        const int32_t *col = ov ? &o_col[(size_t)over_off[(size_t)o]] : &h_col[(size_t)i * cap];
-        const float *val = ov ? &o_val[(size_t)over_off[(size_t)o]] : &h_val[(size_t)i * cap];
-        if (ov) o++;
-        for (int k = 0; k < c; k++, e++) {
-            ecol[(size_t)e] = col[k]; ecost[(size_t)e] = val[k];
-            er[(size_t)e] = ((double)val[k] - (double)ex.v[(size_t)col[k]]) - wp;
-        }
-    }
-    rp[(size_t)n] = e;
-    std::vector<int32_t> sigma((size_t)n);
-    if ((rc = repair_sparse(n, pi.data(), rp.data(), ecol.data(), er.data(), sigma.data(), &ex.free_rows, &ex.changed))) return rc;
-    ex.status = 2;
-    if (ex.changed) {
-        // the total moves by the changed rows' cost differences (float64); u_i = fl32(c_i,sigma(i) - v_sigma(i)) on those rows, v stays
-        std::vector<float> u((size_t)n);
-        double total = 0.0;
-        CYTO_HIP(hipMemcpyAsync(u.data(), d_v + n, nI, hipMemcpyDeviceToHost, stream));
-        CYTO_HIP(hipMemcpyAsync(&total, &j.st()->total, sizeof total, hipMemcpyDeviceToHost, stream));
-        CYTO_HIP(hipStreamSynchronize(stream));
-        double delta = 0.0;
-        for (int i = 0; i < n; i++) {
-            const int js = sigma[(size_t)i];
-            if (js == pi[(size_t)i]) continue;
-            float cs = 0.0f;
-            for (int64_t q = rp[(size_t)i]; q < rp[(size_t)i + 1]; q++) if (ecol[(size_t)q] == js) { cs = ecost[(size_t)q]; break; }
-            delta += (double)cs - (double)cpi[(size_t)i];
-            u[(size_t)i] = cs - ex.v[(size_t)js];
-        }
-        total += delta;
-        std::vector<int32_t> both((size_t)2 * n);
-        for (int i = 0; i < n; i++) { both[(size_t)i] = sigma[(size_t)i]; both[(size_t)n + sigma[(size_t)i]] = i; }
-        CYTO_HIP(hipMemcpyAsync(d_rowsol, both.data(), 2 * nI, hipMemcpyHostToDevice, stream));
-        CYTO_HIP(hipMemcpyAsync(d_v + n, u.data(), nI, hipMemcpyHostToDevice, stream));
-        CYTO_HIP(hipMemcpyAsync(&j.st()->total, &total, sizeof total, hipMemcpyHostToDevice, stream));
-        CYTO_HIP(hipStreamSynchronize(stream));
-    }
-    ex.ms_repair = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return CYTO_OK;
-}
-
 // the counters every solver keeps, as cyto_lap_info reports them
-static void info_from_counters(cyto_lap_info *info, int n, const LapStatus &h) {
+void info_from_counters(cyto_lap_info *info, int n, const LapStatus &h) {
     info->scans_colred = n;
     info->scans_redtransfer = h.counters[C_RT];
     info->scans_arr = h.counters[C_ARR];
@@ -3801,7 +2458,7 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
             hipLaunchKernelGGL(colred_finish<float>, dim3((n + 255) / 256), dim3(256), 0, stream, n, rblocks, j.b_pmin.as<float>(),
                                j.b_parg.as<int32_t>(), d_v, j.b_imin.as<int32_t>(), d_rowsol, d_matches);
         }
-        hipLaunchKernelGGL(colred_assign, dim3((n + 255) / 256), dim3(256), 0, stream, n, j.b_imin.as<int32_t>(), d_rowsol, d_colsol);
+        launch_colred_assign(n, j.b_imin.as<int32_t>(), d_rowsol, d_colsol, stream);
     }
     CYTO_HIP(hipGetLastError());
     CYTO_HIP(hipEventRecord(e1, stream));
@@ -3925,19 +2582,18 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
         double h_gap[3] = {-1.0, -1.0, -1.0};
         ExactRun ex;
         if (((opts.certify && j.info) || opts.exact) && !h.status) {
-            // the float64 certificate (above): one more streaming pass, on the stream, behind the solve
+            // the float64 certificate (lap_exact.hip): one more streaming pass, on the stream, behind the solve
             DevBuf b_viol;
             if ((rc = b_viol.alloc(((size_t)n + 4) * sizeof(double), stream))) return rc;
             const int g = std::max(1, std::min((n + 3) / 4, pl.cache.cus * 8));
-            hipLaunchKernelGGL(dual_gap_rows, dim3(g), dim3(256), 0, stream, n, j.dld, j.dcost, j.rowmap(), d_rowsol, d_v, b_viol.as<double>());
-            hipLaunchKernelGGL(dual_gap_finish, dim3(1), dim3(1024), 0, stream, n, b_viol.as<double>(), b_viol.as<double>() + n);
-            CYTO_HIP(hipGetLastError());
+            if ((rc = certify_launch(n, j.dld, j.dcost, j.rowmap(), d_rowsol, d_v, b_viol.as<double>(), g, stream))) return rc;
             // the exact option: the near-tight edges right behind it (the kernel reads the gap on the device)
-            if (opts.exact && (rc = exact_emit(ex, n, opts.exact == 1 ? EXACT_SLOTS_DEFAULT : opts.exact, j, b_viol.as<double>() + n, g, stream)))
+            const ExactView xv = {j.dcost, j.dld, j.rowmap(), d_rowsol, d_v, j.st()};
+            if (opts.exact && (rc = exact_emit(ex, n, opts.exact == 1 ? EXACT_SLOTS_DEFAULT : opts.exact, xv, b_viol.as<double>() + n, g, stream)))
                 return rc;
             CYTO_HIP(hipMemcpyAsync(h_gap, b_viol.as<double>() + n, sizeof h_gap, hipMemcpyDeviceToHost, stream));
             CYTO_HIP(hipStreamSynchronize(stream));
-            if (opts.exact && (rc = exact_repair(ex, n, j, h_gap[0], g, stream))) return rc;
+            if (opts.exact && (rc = exact_repair(ex, n, xv, h_gap[0], g, stream))) return rc;
         }
         if (j.rowsol) CYTO_HIP(hipMemcpy(j.rowsol, d_rowsol, nI, hipMemcpyDeviceToHost));
         if (j.colsol) CYTO_HIP(hipMemcpy(j.colsol, d_rowsol + n, nI, hipMemcpyDeviceToHost));
@@ -3991,225 +2647,6 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
     return CYTO_OK;
 }
 
-// ---- float64 (the force_doubles / lapjv_compat precision): the generic chain, one problem ----
-template <typename T, int CH, bool LDSCS>
-static int launch_chain(const ChainArgs<T> &args, hipStream_t stream) {
-    const size_t shmem = LDSCS ? (((size_t)args.n * sizeof(int32_t) + 15) / 16) * 16 : 16;
-    auto kern = jv_chain<T, CH, LDSCS>;
-    int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(kern));
-    if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(1), dim3(BLOCK), shmem, stream, args);
-    CYTO_HIP(hipGetLastError());
-    return CYTO_OK;
-}
-
-static int lap_solve_f32(int n, const float *cost, int64_t ld, int cost_on_device, int32_t *rowsol, int32_t *colsol,
-                         float *u, float *v, double *total, cyto_lap_info *info, int device_id, hipStream_t stream,
-                         const cyto_lap_opts &opts);
-__global__ void narrow_f64_to_f32(int n, int64_t lds_, const double *__restrict__ src, int64_t ldd, float *__restrict__ dst);
-__global__ __launch_bounds__(256) void widen_prices(int n, const float *__restrict__ v32, double *__restrict__ v64) {
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j < n) v64[j] = (double)v32[j];
-}
-
-// float64 (the precision of `lapjv(cost, force_doubles=True)` and of `lap.lapjv`, linear_assignment_solvers.py:13-15, 36).
-// By default WARM-started (oracle/jv_oracle.c: jv_oracle_warm_f64): the classic float64 solve spends nearly all its time in the
-// price wars of the row reduction, and the prices those wars converge to are known to float32 resolution beforehand -- the matrix is
-// narrowed on the device, the float32 wide solver runs on it, its prices (widened exactly) are the start, every row free; the
-// float64 augmenting row reduction then takes ~1.2 n steps instead of ~240 n and leaves a handful of rows to the augmentation.
-// cyto_lap_opts.mode = 1 (or any chain option): the cold classic chain, the parity reference of rounds 1-3.
-static int lap_solve_f64(int n, const double *cost, int64_t ld, int cost_on_device, int32_t *rowsol, int32_t *colsol,
-                         double *u, double *v, double *total, cyto_lap_info *info, int device_id, hipStream_t stream,
-                         const cyto_lap_opts &opts, const float *warm_prices_host = nullptr) {
-    // warm_prices_host: the start prices are the caller's (the float32 solve of this very matrix: lap_polish_f64) -- no narrowing, no
-    // float32 solve here
-    typedef double T;
-    constexpr int VW = VecOf<T>::W;
-    if (n <= 0 || !cost || ld < n) return CYTO_ERR_BAD_ARG;
-    int rc = check_opts(opts);
-    if (rc) return rc;
-    if (opts.exact) return CYTO_ERR_BAD_ARG;             // (the float32 solve's option: a float64 solve is exact already)
-    if (n > FAST_NMAX) return CYTO_ERR_UNSUPPORTED;
-    if ((rc = select_device(device_id))) return rc;
-    Events<3> ev;
-    if ((rc = ev.create())) return rc;
-    const hipEvent_t e0 = ev[0], e1 = ev[1], e2 = ev[2];
-    DevBuf staged;
-    const T *dcost = cost;
-    int64_t dld = ld;
-    const bool aligned = cost_on_device && (ld % VW == 0) && ((reinterpret_cast<uintptr_t>(cost) & 15) == 0);
-    if (!aligned) {
-        dld = ((int64_t)n + VW - 1) / VW * VW;
-        if ((rc = staged.alloc((size_t)n * dld * sizeof(T), stream))) return rc;
-        CYTO_HIP(hipMemcpy2DAsync(staged.p, dld * sizeof(T), cost, ld * sizeof(T), (size_t)n * sizeof(T), n,
-                                  cost_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
-        dcost = staged.as<T>();
-    }
-    const int colblocks = (n + 256 * VW - 1) / (256 * VW);
-    int rowblocks = (2048 + colblocks - 1) / colblocks;
-    rowblocks = max(1, min(rowblocks, (n + 15) / 16));
-    const int rows_per_block = (n + rowblocks - 1) / rowblocks;
-    rowblocks = (n + rows_per_block - 1) / rows_per_block;
-    DevBuf b_fws, b_iws, b_imin, b_pmin, b_parg, b_misc;
-    const size_t nT = (size_t)n * sizeof(T), nI = (size_t)n * sizeof(int32_t);
-    if ((rc = b_fws.alloc(6 * nT + 64, stream)) || (rc = b_iws.alloc(10 * nI + 64, stream)) || (rc = b_imin.alloc(nI, stream)) ||
-        (rc = b_pmin.alloc((size_t)rowblocks * nT, stream)) || (rc = b_parg.alloc((size_t)rowblocks * nI, stream)) ||
-        (rc = b_misc.alloc(sizeof(LapStatus), stream)))
-        return rc;
-    T *d_v = b_fws.as<T>(), *d_u = b_fws.as<T>() + n;
-    int32_t *d_rowsol = b_iws.as<int32_t>(), *d_colsol = d_rowsol + n, *d_matches = d_rowsol + 2 * (size_t)n;
-    LapStatus *st = b_misc.as<LapStatus>();
-    CYTO_HIP(hipMemsetAsync(st, 0, sizeof(LapStatus), stream));
-    CYTO_HIP(hipMemsetAsync(d_rowsol, 0xFF, nI, stream));
-    CYTO_HIP(hipMemsetAsync(d_matches, 0, nI, stream));
-    CYTO_HIP(hipEventRecord(e0, stream));
-    hipLaunchKernelGGL(colred_partial<T>, dim3(colblocks, rowblocks), dim3(256), 0, stream, n, dld, dcost, rows_per_block,
-                       b_pmin.as<T>(), b_parg.as<int32_t>(), &st->nonfinite, n, (const int32_t *)nullptr, (const int32_t *)nullptr);
-    int h_nonfinite = 0;
-    CYTO_HIP(hipMemcpyAsync(&h_nonfinite, &st->nonfinite, sizeof(int), hipMemcpyDeviceToHost, stream));
-    CYTO_HIP(hipStreamSynchronize(stream));
-    if (h_nonfinite) return CYTO_ERR_NONFINITE;
-    bool warm = opts.mode != 1 && opts.chain_variant == 0 && opts.augmentation == 0 && n >= 2;
-    double ms_warm = 0.0;
-    if (warm) {
-        // the float32 wide solve of the narrowed matrix: its prices are the start
-        const int64_t ld32 = ((int64_t)n + 3) & ~(int64_t)3;
-        DevBuf d32, dv32;
-        std::vector<float> h_v32((size_t)n);
-        cyto_lap_info li32;
-        if (warm_prices_host) {
-            memset(&li32, 0, sizeof li32);
-            memcpy(h_v32.data(), warm_prices_host, (size_t)n * sizeof(float));
-            if ((rc = dv32.alloc((size_t)n * sizeof(float), stream))) return rc;
-            rc = CYTO_OK;
-        } else {
-        if ((rc = d32.alloc((size_t)n * ld32 * sizeof(float), stream)) || (rc = dv32.alloc((size_t)n * sizeof(float), stream))) return rc;
-        hipLaunchKernelGGL(narrow_f64_to_f32, dim3((n + 255) / 256 > 64 ? 64 : (n + 255) / 256, n > 32768 ? 32768 : n), dim3(256), 0, stream,
-                           n, dld, dcost, ld32, d32.as<float>());
-        CYTO_HIP(hipGetLastError());
-        rc = lap_solve_f32(n, d32.as<float>(), ld32, 1, nullptr, nullptr, nullptr, h_v32.data(), nullptr, &li32, device_id, stream, k_default_opts);
-        }
-        if (rc == CYTO_ERR_NONFINITE) { warm = false; rc = CYTO_OK; }       // finite float64 costs beyond float32's range: the cold start
-        else if (rc) return rc;
-        else {
-            ms_warm = li32.ms_total;
-            CYTO_HIP(hipMemcpyAsync(dv32.p, h_v32.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice, stream));
-            hipLaunchKernelGGL(widen_prices, dim3((n + 255) / 256), dim3(256), 0, stream, n, dv32.as<float>(), d_v);
-            CYTO_HIP(hipMemsetAsync(d_colsol, 0xFF, nI, stream));     // nothing assigned, every row free (rowsol / matches: above)
-            CYTO_HIP(hipGetLastError());
-            CYTO_HIP(hipStreamSynchronize(stream));                    // (h_v32 / dv32 / d32 are locals)
-        }
-    }
-    if (!warm) {
-        hipLaunchKernelGGL(colred_finish<T>, dim3((n + 255) / 256), dim3(256), 0, stream, n, rowblocks, b_pmin.as<T>(),
-                           b_parg.as<int32_t>(), d_v, b_imin.as<int32_t>(), d_rowsol, d_matches);
-        hipLaunchKernelGGL(colred_assign, dim3((n + 255) / 256), dim3(256), 0, stream, n, b_imin.as<int32_t>(), d_rowsol, d_colsol);
-    }
-    CYTO_HIP(hipEventRecord(e1, stream));
-    ChainArgs<T> ca;
-    ca.n = n; ca.ld = dld; ca.cost = dcost; ca.v = d_v; ca.u = d_u;
-    ca.rowsol = d_rowsol; ca.colsol = d_colsol; ca.matches = d_matches;
-    ca.freerows = d_rowsol + 3 * (size_t)n; ca.rtrows = d_rowsol + 4 * (size_t)n; ca.pred = d_rowsol + 5 * (size_t)n;
-    ca.total = &st->total; ca.counters = st->counters; ca.status = &st->status;
-    ca.dwork = d_v + 4 * (size_t)n; ca.lvl = d_rowsol + 7 * (size_t)n;
-    ca.cache_col = nullptr; ca.cache_val = nullptr; ca.cs_lds = 0; ca.v_lds = 0;
-    // register-resident chain while it does not spill (n <= 4096), else everything streams from L2 -- with row caches
-    // against the post-column-reduction prices for REDUCTION TRANSFER and AUGMENTING ROW REDUCTION
-    // (opts.chain_variant == 2: without them, every scan reads its row)
-    const int64_t per = (int64_t)VW * BLOCK;
-    DevBuf b_ccol, b_cval;
-    if (n <= 2 * per && opts.chain_variant == 0) rc = launch_chain<T, 2, true>(ca, stream);
-    else {
-        if (opts.chain_variant != 2) {
-            if ((rc = b_ccol.alloc((size_t)n * WC_KC * sizeof(uint32_t), stream)) || (rc = b_cval.alloc((size_t)n * WC_KC * sizeof(T), stream))) return rc;
-            hipLaunchKernelGGL(build_row_caches_wide<T>, dim3(n), dim3(256), 0, stream, n, dld, dcost, d_v, b_ccol.as<uint32_t>(), b_cval.as<T>());
-            ca.cache_col = b_ccol.as<uint32_t>(); ca.cache_val = b_cval.as<T>();
-        }
-        // (chain_variant 3: the caches with colsol in global memory -- what n > 65 535 uses -- forced for the test-suite)
-        ca.cs_lds = (ca.cache_col && n <= 65535 && opts.chain_variant != 3) ? 1 : 0;
-        const size_t vbytes = (((size_t)n * sizeof(T)) + 15) & ~(size_t)15, csbytes = (((size_t)n * 2 + 15) / 16) * 16;
-        ca.v_lds = (ca.cs_lds && vbytes + csbytes <= (size_t)LDS_DYNAMIC_MAX) ? 1 : 0;
-        const size_t cs_lds = ca.cs_lds ? csbytes + (ca.v_lds ? vbytes : 0) : 16;
-        if ((rc = set_max_dynamic_lds(reinterpret_cast<const void *>(jv_chain_stream<T>)))) return rc;
-        hipLaunchKernelGGL(jv_chain_stream<T>, dim3(1), dim3(BLOCK), cs_lds, stream, ca);
-        rc = hipGetLastError() == hipSuccess ? CYTO_OK : CYTO_ERR_HIP;
-    }
-    if (rc) return rc;
-    CYTO_HIP(hipEventRecord(e2, stream));
-    CYTO_HIP(hipStreamSynchronize(stream));
-    LapStatus h;
-    CYTO_HIP(hipMemcpy(&h, st, sizeof h, hipMemcpyDeviceToHost));
-    if (rowsol) CYTO_HIP(hipMemcpy(rowsol, d_rowsol, nI, hipMemcpyDeviceToHost));
-    if (colsol) CYTO_HIP(hipMemcpy(colsol, d_colsol, nI, hipMemcpyDeviceToHost));
-    if (u) CYTO_HIP(hipMemcpy(u, d_u, nT, hipMemcpyDeviceToHost));
-    if (v) CYTO_HIP(hipMemcpy(v, d_v, nT, hipMemcpyDeviceToHost));
-    if (total) *total = h.total;
-    if (info) {
-        memset(info, 0, sizeof *info);
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, e0, e1); info->ms_colred = ms;      // (warm start: the float32 solve's launches and waits included)
-        (void)hipEventElapsedTime(&ms, e1, e2); info->ms_chain = ms;
-        info->ms_total = info->ms_colred + info->ms_chain;
-        info->f64_warm = warm ? 1 : 0; info->f64_warm_ms = ms_warm;
-        info_from_counters(info, n, h);
-        info->hbm_row_reads = n + h.counters[C_ROWS_READ];
-        info->aug_handover = -1;
-        info->row_groups = n;
-    }
-    return h.status ? CYTO_ERR_INTERNAL : CYTO_OK;
-}
-
-// The float64 POLISH of a float32 solve (cyto_lap_opts.polish): the float32 solvers compare rounded reduced costs, so on a near-tie
-// (two assignments whose totals differ by less than the rounding of the float32 duals, ~1e-8) which optimal-looking assignment comes
-// out depends on their constants (DESIGN "Tried", round 5: phases ending at 128 rows instead of 64 left the few-cell-type 20 000^2
-// instance 2e-8 above its optimum).  When the certificate (dual_gap_rows) cannot prove the result optimal, the matrix is widened to
-// float64 on the device (exactly), the float32 prices are the start with every row free, and the float64 augmenting row reduction and
-// augmentation of the force_doubles path run from there (any prices with nothing assigned are a valid JV state): ~1.2 n steps.  The
-// result is the optimum of the float32 matrix in float64 arithmetic -- indices that depend on the MATRIX, not on the float32 solver.
-// Costs n^2 x 8 bytes of device memory and several times the solve: an option, not the default.
-__global__ __launch_bounds__(256) void widen_f32_rows(int n, int64_t lds_, const float *__restrict__ src, const int32_t *__restrict__ rowmap,
-                                                      int64_t ldd, double *__restrict__ dst) {
-    for (int64_t row = blockIdx.y; row < n; row += gridDim.y) {
-        const float *__restrict__ r = src + (int64_t)(rowmap ? rowmap[row] : row) * lds_;
-        for (int c = blockIdx.x * 256 + threadIdx.x; c < n; c += gridDim.x * 256) dst[row * ldd + c] = (double)r[c];
-    }
-}
-static int lap_polish_f64(int n, const float *cost, int64_t ld, int cost_on_device, const int32_t *rowmap_host, int nu, const float *v32,
-                          int32_t *rowsol, int32_t *colsol, float *u, float *v, double *total, double *ms_out, int device_id,
-                          hipStream_t stream) {
-    int rc = select_device(device_id);
-    if (rc) return rc;
-    const int nstored = rowmap_host ? nu : n;
-    const int64_t ldd = ((int64_t)n + 1) & ~(int64_t)1;
-    DevBuf d64, staged, d_map;
-    const float *dsrc = cost;
-    int64_t dls = ld;
-    if ((rc = d64.alloc((size_t)n * ldd * sizeof(double), stream))) return rc;
-    if (!cost_on_device) {
-        if ((rc = staged.alloc((size_t)nstored * n * sizeof(float), stream))) return rc;
-        CYTO_HIP(hipMemcpy2DAsync(staged.p, (size_t)n * sizeof(float), cost, (size_t)ld * sizeof(float), (size_t)n * sizeof(float), nstored,
-                                  hipMemcpyHostToDevice, stream));
-        dsrc = staged.as<float>(); dls = n;
-    }
-    if (rowmap_host) {
-        if ((rc = d_map.alloc((size_t)n * sizeof(int32_t), stream))) return rc;
-        CYTO_HIP(hipMemcpyAsync(d_map.p, rowmap_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    }
-    hipLaunchKernelGGL(widen_f32_rows, dim3((n + 255) / 256 > 64 ? 64 : (n + 255) / 256, n > 32768 ? 32768 : n), dim3(256), 0, stream, n, dls, dsrc,
-                       rowmap_host ? d_map.as<int32_t>() : (const int32_t *)nullptr, ldd, d64.as<double>());
-    CYTO_HIP(hipGetLastError());
-    CYTO_HIP(hipStreamSynchronize(stream));
-    staged.reset();
-    std::vector<double> u64((size_t)n), v64((size_t)n);
-    cyto_lap_info li = {};
-    rc = lap_solve_f64(n, d64.as<double>(), ldd, 1, rowsol, colsol, u64.data(), v64.data(), total, &li, device_id, stream, k_default_opts, v32);
-    if (rc) return rc;
-    if (u) for (int i = 0; i < n; i++) u[i] = (float)u64[(size_t)i];
-    if (v) for (int i = 0; i < n; i++) v[i] = (float)v64[(size_t)i];
-    if (ms_out) *ms_out = li.ms_total;
-    return CYTO_OK;
-}
-
 // one float32 problem = a batch of one
 static int lap_solve_f32_one(int n, const float *cost, int64_t ld, int cost_on_device, const int32_t *rowmap_host, int nu, int32_t *rowsol,
                              int32_t *colsol, float *u, float *v, double *total, cyto_lap_info *info, int device_id, hipStream_t stream,
@@ -4233,9 +2670,9 @@ static int lap_solve_f32_one(int n, const float *cost, int64_t ld, int cost_on_d
     if (info && (info != &li)) *info = li;
     return rc;
 }
-static int lap_solve_f32(int n, const float *cost, int64_t ld, int cost_on_device, int32_t *rowsol, int32_t *colsol,
-                         float *u, float *v, double *total, cyto_lap_info *info, int device_id, hipStream_t stream,
-                         const cyto_lap_opts &opts) {
+int lap_solve_f32(int n, const float *cost, int64_t ld, int cost_on_device, int32_t *rowsol, int32_t *colsol,
+                  float *u, float *v, double *total, cyto_lap_info *info, int device_id, hipStream_t stream,
+                  const cyto_lap_opts &opts) {
     return lap_solve_f32_one(n, cost, ld, cost_on_device, nullptr, 0, rowsol, colsol, u, v, total, info, device_id, stream, opts);
 }
 
@@ -4264,6 +2701,12 @@ __global__ __launch_bounds__(256) void narrow_f64_to_f32(int n, int64_t lds_, co
         for (int c = blockIdx.x * 256 + threadIdx.x; c < n; c += gridDim.x * 256) dst[row * ldd + c] = (float)src[row * lds_ + c];
 }
 
+int narrow_to_f32(int n, int64_t ld_src, const double *src, int64_t ld_dst, float *dst, hipStream_t stream) {
+    hipLaunchKernelGGL(narrow_f64_to_f32, matrix_copy_grid(n), dim3(256), 0, stream, n, ld_src, src, ld_dst, dst);
+    CYTO_HIP(hipGetLastError());
+    return CYTO_OK;
+}
+
 }  // namespace cyto
 
 extern "C" {
@@ -4282,9 +2725,7 @@ int cyto_lap_f32_from_f64(int n, const double *cost_host, int64_t ld, int32_t *r
     if ((rc = d64.alloc((size_t)n * n * sizeof(double), stream)) || (rc = d32.alloc((size_t)n * ldd * sizeof(float), stream))) return rc;
     CYTO_HIP(hipMemcpy2DAsync(d64.p, (size_t)n * sizeof(double), cost_host, (size_t)ld * sizeof(double), (size_t)n * sizeof(double), n,
                               hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(cyto::narrow_f64_to_f32, dim3((n + 255) / 256 > 64 ? 64 : (n + 255) / 256, n > 32768 ? 32768 : n), dim3(256), 0,
-                       stream, n, (int64_t)n, d64.as<double>(), ldd, d32.as<float>());
-    CYTO_HIP(hipGetLastError());
+    if ((rc = cyto::narrow_to_f32(n, (int64_t)n, d64.as<double>(), ldd, d32.as<float>(), stream))) return rc;
     CYTO_HIP(hipStreamSynchronize(stream));
     d64.reset();                                           // the float64 copy is not needed during the solve
     return cyto::lap_solve_f32(n, d32.as<float>(), ldd, 1, rowsol, colsol, u, v, total, info, device_id, stream, cyto::k_default_opts);
@@ -4316,17 +2757,6 @@ int cyto_lap_f32_opts(int n, const float *cost, int64_t ld, int cost_on_device, 
 int cyto_lap_f64_opts(int n, const double *cost, int64_t ld, int cost_on_device, int32_t *rowsol, int32_t *colsol,
                       double *u, double *v, double *total, cyto_lap_info *info, int device_id, void *stream, const cyto_lap_opts *opts) {
     return cyto::lap_solve_f64(n, cost, ld, cost_on_device, rowsol, colsol, u, v, total, info, device_id, reinterpret_cast<hipStream_t>(stream), opts ? *opts : cyto::k_default_opts);
-}
-
-// the host half of cyto_lap_opts.exact on its own (no device): the test suite pins it against an independent exact solver
-int cyto_lap_repair_sparse(int n, const int32_t *rowsol, const int64_t *row_ptr, const int32_t *cols, const double *r, int32_t *rowsol_out) {
-    try {
-        return cyto::repair_sparse(n, rowsol, row_ptr, cols, r, rowsol_out, nullptr, nullptr);
-    } catch (const std::bad_alloc &) {
-        return CYTO_ERR_NOMEM;
-    } catch (...) {
-        return CYTO_ERR_INTERNAL;
-    }
 }
 
 }  // extern "C"

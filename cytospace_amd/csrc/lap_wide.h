@@ -17,7 +17,7 @@ struct CachePlan {
 int build_caches(const CachePlan &cp, int n, int64_t ld, const float *cost, const int32_t *rowmap, const float *v, uint32_t *cache_col,
                  float *cache_val, const int32_t *same, hipStream_t stream);
 
-// One problem of a batch as the float32 driver has set it up (lap_jv.hip: F32Job, after the column reduction).  Device memory.
+// One problem of a batch as the float32 driver has set it up (lap_jv.hip: F32Job, private to it, after the column reduction).  Device memory.
 struct WideJob {
     const float *cost; int64_t ld;
     const int32_t *rowmap;              // [n] LAP row i reads stored row rowmap[i], or null

@@ -25,6 +25,14 @@ def test_library_exports_every_declared_symbol():
     assert L.cyto_strerror(2).decode() == "cost matrix contains NaN or Inf"
 
 
+def test_build_source_list_is_the_csrc_directory():
+    # every csrc/*.hip is compiled into the library, and every entry of the list exists
+    from cytospace_amd import build
+    on_disk = sorted(f for f in os.listdir(build.CSRC) if f.endswith(".hip"))
+    assert sorted(build.SOURCES) == on_disk
+    assert len(set(build.SOURCES)) == len(build.SOURCES)
+
+
 def test_status_to_exception_mapping():
     from cytospace_amd import _lib
     _lib.lib()

@@ -9,5 +9,7 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 name=$1; shift
 python -m cytospace_amd.build > /dev/null
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-result "$@" -c -o $R/cytospace_amd/build/lap_wide_$name.o $R/cytospace_amd/csrc/lap_wide.hip
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/cytospace_amd/build/libcytohip_$name.so $R/cytospace_amd/build/{core,lap_jv,cost,batch,comm,downsample,table,mtx}.o $R/cytospace_amd/build/lap_wide_$name.o -L/opt/rocm/lib -lrccl -lpthread
+# (the other objects: build.SOURCES, so that a new source file cannot be forgotten here)
+objs=$(python -c "import os; from cytospace_amd import build as b; print(' '.join(os.path.join(b.OBJ, s.replace('.hip', '.o')) for s in b.SOURCES if s != 'lap_wide.hip'))")
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/cytospace_amd/build/libcytohip_$name.so $objs $R/cytospace_amd/build/lap_wide_$name.o -L/opt/rocm/lib -lrccl -lpthread
 ls -la $R/cytospace_amd/build/libcytohip_$name.so
