@@ -127,6 +127,10 @@ def lib():
         if hasattr(L, "cyto_wide_embedded_solves"):          # (absent from older A/B builds loaded through CYTOHIP_LIB)
             L.cyto_wide_embedded_solves.argtypes = []
             L.cyto_wide_embedded_solves.restype = ctypes.c_longlong
+        for name in ("cyto_fused_cache_solves", "cyto_fused_cache_fallback_rows"):
+            if hasattr(L, name):                             # (absent from older A/B builds loaded through CYTOHIP_LIB)
+                getattr(L, name).argtypes = []
+                getattr(L, name).restype = ctypes.c_longlong
         L.cyto_trim_device_cache.argtypes = [i32]
         L.cyto_trim_device_cache.restype = ctypes.c_int
         dp = ctypes.POINTER(ctypes.c_double)
@@ -222,6 +226,16 @@ def check(status):
     if status == 5:
         msg += ": " + L.cyto_last_hip_error().decode()
     raise _EXC.get(status, CytoHipError)(f"cytohip status {status}: {msg}")
+
+
+def fused_cache_solves():
+    """Solves of this process whose first row caches came from the column reduction's pass (cyto_fused_cache_solves)."""
+    return int(lib().cyto_fused_cache_solves())
+
+
+def fused_cache_fallback_rows():
+    """Rows of those solves that the row builder swept all the same (cyto_fused_cache_fallback_rows)."""
+    return int(lib().cyto_fused_cache_fallback_rows())
 
 
 def wide_embedded_solves():

@@ -31,6 +31,7 @@
 #include "lap_exact.h"
 #include "lap_wide.h"
 #include <math.h>
+#include <atomic>
 #include <cmath>
 #include <type_traits>
 #include <vector>
@@ -666,16 +667,20 @@ template <int U>
 __global__ __launch_bounds__(64 * CBW) void build_row_caches_wave(int n, int64_t ld, const float *__restrict__ cost,
                                                                  const float *__restrict__ v, uint32_t *__restrict__ cache_col,
                                                                  float *__restrict__ cache_val, const int32_t *__restrict__ rowmap,
-                                                                 const int32_t *__restrict__ same_prev, int stream) {
+                                                                 const int32_t *__restrict__ same_prev, int stream,
+                                                                 const int32_t *__restrict__ rowlist, int count) {
+    // rowlist (or null: all n rows): the `count` rows to build, in any order -- a wave takes list positions where it takes row indices
     __shared__ CbStage stage[CBW];
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // (scalar: row bases and descriptors stay in SGPRs)
     CbStage &st = stage[w];
     const int gw = (int)blockIdx.x * CBW + w, nw = (int)gridDim.x * CBW;
-    const int per = (n + nw - 1) / nw, i_end = min(n, (gw + 1) * per);      // (a contiguous range of rows per wave)
+    const int nrows = rowlist ? count : n;
+    const int per = (nrows + nw - 1) / nw, i_end = min(nrows, (gw + 1) * per);      // (a contiguous range of rows per wave)
     const int nquad = (n + 3) >> 2;
     const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(v), 0, nquad * 16, 0x00020000);
     float tau_guess = INFINITY, delta = 0.0f;
-    for (int i = gw * per; i < i_end; i++) {
+    for (int ii = gw * per; ii < i_end; ii++) {
+        const int i = rowlist ? __builtin_amdgcn_readfirstlane(rowlist[ii]) : ii;
         if (same_prev && same_prev[i]) continue;                          // a copy of the previous row: replicate_group_caches
         const float *__restrict__ row = cost + row_off(rowmap, i, ld);
         const __amdgpu_buffer_rsrc_t rrow = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(row), 0, (int)(ld * 4), 0x00020000);
@@ -762,6 +767,231 @@ __global__ __launch_bounds__(64 * CBW) void build_row_caches_wave(int n, int64_t
         cache_col[(int64_t)i * KC + lane] = kc;
         cache_val[(int64_t)i * KC + lane] = kv;
     }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// FIRST caches from the column reduction's own pass (float32, the wide solver, no row map).  The column reduction
+// and the first cache build each stream the whole matrix, for a result that needs every entry once.  Here the column pass lists,
+// per row, the few hundred columns that can be in the row's cache (colred_partial_append), against an UPPER bound w of
+// the prices (fused_w: the column minima over the first rows) and a per-row threshold theta (fused_theta); when the prices v exist,
+// fused_fixup turns each list into an ordinary cache.  Exact: w >= v and rounding is monotone, so fl(c - v[j]) >= fl(c - w[j]);
+// the list { j : fl(c - w[j]) < theta } therefore holds EVERY column with fl(c - v[j]) < theta, and any floor tau <= theta with at
+// most 63 listed columns below it gives the cache { j : fl(c - v[j]) < tau }, floor tau.  Rows the lists cannot certify (list over
+// its cap, fewer than min_kept columns below tau) go on a row list for build_row_caches_wave.  min_kept (fused_min_kept) is 48 from
+// 4 096 columns on, not the contract's 16: the row reduction pays for every thin cache with full-row bids (50 000^2: rows accepted
+// from 16 columns on -- 3 % of them end below 63 -- 240 full-row bids and 41.7 ms a solve; from 48 on 3 bids and 38.3 ms; the row
+// builder's own caches 79 bids and 39.8 ms).
+constexpr int FUSED_S = 2048;       // columns of a row that fused_theta reads (64 lanes x 8 quads)
+constexpr int FUSED_TARGET = 190;   // listed columns per row aimed at
+constexpr int COLRED_CAP = 512;     // entries of a row's candidate list
+struct ColredAppend {
+    const float *w; const float *theta;
+    int32_t *cnt; uint2 *list;      // [n], [n][COLRED_CAP]
+};
+// colred_partial (lap_chain.h) for float32 without a row map, which also LISTS the candidates: every column with
+// fl(c - w[j]) < theta[r] is appended to list[r] as (column, raw cost bits).  A wave whose ballot shows a hit takes ONE returning
+// atomicAdd on cnt[r] for that row; its lanes take positions by ballot prefix and store while the position is below COLRED_CAP (cnt
+// keeps counting: a row over the cap is built by the row builder instead).  Column minima, the lowest row on ties, the non-finite
+// flag and pmin / parg are colred_partial's.  Every lane stays for the ballots: past the last quad it re-reads that quad and owns no
+// column.
+__global__ __launch_bounds__(256) void colred_partial_append(int n, int64_t ld, const float *__restrict__ cost, int rows_per_block,
+                                                             float *__restrict__ pmin, int32_t *__restrict__ parg,
+                                                             int *__restrict__ nonfinite, int nrows, ColredAppend ap) {
+    constexpr int VW = 4, RU = 4;                                      // RU: rows of a group (two groups in flight per wave)
+    const int q = blockIdx.x * 256 + threadIdx.x;                      // vector-column index
+    const int col0 = q * VW, ql = min(q, (n - 1) >> 2);
+    const int r0 = blockIdx.y * rows_per_block;
+    const int r1 = min(nrows, r0 + rows_per_block);
+    const int lane = threadIdx.x & 63;
+    const uint64_t lt = (1ull << lane) - 1ull;
+    float mn[VW], we[VW];
+    int32_t arg[VW];
+    bool bad = false;
+#pragma unroll
+    for (int e = 0; e < VW; e++) { mn[e] = INFINITY; arg[e] = r0; we[e] = col0 + e < n ? ap.w[col0 + e] : 0.0f; }
+    // RU rows at a time, one group ahead: the NEXT group's loads are issued first, then this group's hits are found and lanes
+    // 0 .. RU - 1 take the atomics of its RU rows in ONE instruction, so that the wait for their positions is also the wait for
+    // the next group's loads (the latencies overlap); then the stores go out.  With stores outstanding beside loads a wave can
+    // only wait for everything, so the group's registers are touched (the empty asm) BEFORE the next loads are issued: that wait
+    // finds nothing but the last stores.  Past the block's last row the last row is read again, with a threshold nothing lies
+    // below (a row seen twice changes no minimum).
+    auto row_of = [&](int k) { return min(r0 + k, r1 - 1); };
+    auto load_row = [&](int r) { return *(reinterpret_cast<const float4 *>(cost + (int64_t)r * ld) + ql); };
+    float4 xn[RU]; float thn[RU];                                      // (the thresholds come with the rows: they are vector loads too)
+#pragma unroll
+    for (int u = 0; u < RU; u++) { xn[u] = load_row(row_of(u)); thn[u] = ap.theta[row_of(u)]; }
+    for (int k = 0; r0 + k < r1; k += RU) {
+        float4 x[RU]; float thr[RU]; int rr[RU];
+#pragma unroll
+        for (int u = 0; u < RU; u++) {
+            x[u] = xn[u]; thr[u] = thn[u]; rr[u] = row_of(k + u);
+            asm volatile("" : "+v"(x[u].x), "+v"(x[u].y), "+v"(x[u].z), "+v"(x[u].w), "+v"(thr[u]) :: "memory");
+        }
+#pragma unroll
+        for (int u = 0; u < RU; u++) { xn[u] = load_row(row_of(k + RU + u)); thn[u] = ap.theta[row_of(k + RU + u)]; }
+        uint64_t b[RU][VW]; int tot[RU];
+        int my_tot = 0, my_row = 0;
+#pragma unroll
+        for (int u = 0; u < RU; u++) {
+            tot[u] = 0;
+            const float th = r0 + k + u < r1 ? thr[u] : -INFINITY;
+#pragma unroll
+            for (int e = 0; e < VW; e++) {
+                const float xe = vec_get<float>(x[u], e);
+                if (col0 + e < n) bad |= !__builtin_isfinite(xe);
+                if (xe < mn[e]) { mn[e] = xe; arg[e] = rr[u]; }
+                b[u][e] = __ballot(col0 + e < n && xe - we[e] < th);
+                tot[u] += __popcll(b[u][e]);
+            }
+            if (lane == u) { my_tot = tot[u]; my_row = rr[u]; }
+        }
+        uint32_t old = 0;
+        if (my_tot) old = (uint32_t)atomicAdd(ap.cnt + my_row, my_tot);
+        asm volatile("" : "+v"(old) :: "memory");                      // (the one wait: the positions and the next group's loads)
+#pragma unroll
+        for (int u = 0; u < RU; u++) {
+            if (!tot[u]) continue;                                     // (wave-uniform)
+            int pos = __builtin_amdgcn_readlane((int)old, u);
+            uint2 *lst = ap.list + (int64_t)rr[u] * COLRED_CAP;
+#pragma unroll
+            for (int e = 0; e < VW; e++) {
+                const int p = pos + __popcll(b[u][e] & lt);
+                if (((b[u][e] >> lane) & 1ull) && (unsigned)p < (unsigned)COLRED_CAP)
+                    lst[p] = make_uint2((uint32_t)(col0 + e), __float_as_uint(vec_get<float>(x[u], e)));
+                pos += __popcll(b[u][e]);
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < VW; e++) {
+        if (col0 + e < n) {
+            pmin[(int64_t)blockIdx.y * n + col0 + e] = mn[e];
+            parg[(int64_t)blockIdx.y * n + col0 + e] = arg[e];
+        }
+    }
+    if (bad) atomicOr(nonfinite, 1);
+}
+
+
+// columns a row must keep: half of what theta aims at below it (c0 of the first FUSED_S columns: c0 n / FUSED_S of the row), 16 ... 48
+static int fused_min_kept(int n) {
+    const double c0 = std::min(49.0, std::max(6.0, (double)FUSED_TARGET * FUSED_S / n));
+    return (int)std::min(48.0, std::max(16.0, 0.5 * c0 * n / FUSED_S));
+}
+
+__global__ void fused_w(int n, int nblocks, const float *__restrict__ pmin, float *__restrict__ w) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    float mn = pmin[j];
+    for (int b = 1; b < nblocks; b++) mn = fminf(mn, pmin[(int64_t)b * n + j]);
+    w[j] = mn;
+}
+
+// theta[i]: the (i0 + 1)-th smallest of the 64 lane minima of fl(c - w) over the row's first FUSED_S columns, i0 as in cb_stream for
+// c0 = FUSED_TARGET * FUSED_S / n columns wanted below it among those (6 at least, 49 at most).  n >= FUSED_S.
+__global__ __launch_bounds__(256) void fused_theta(int n, int64_t ld, const float *__restrict__ cost, const float *__restrict__ w,
+                                                   float *__restrict__ theta) {
+    const int lane = threadIdx.x & 63, i = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    if (i >= n) return;
+    const float4 *row = reinterpret_cast<const float4 *>(cost + (int64_t)i * ld), *w4 = reinterpret_cast<const float4 *>(w);
+    float m = INFINITY;
+#pragma unroll
+    for (int u = 0; u < FUSED_S / 256; u++) {
+        const float4 x = row[64 * u + lane], y = w4[64 * u + lane];
+        m = fminf(m, fminf(fminf(x.x - y.x, x.y - y.y), fminf(x.z - y.z, x.w - y.w)));
+    }
+    const float srt = cb_sort64(m, lane);
+    const float c0 = fminf(49.0f, fmaxf(6.0f, (float)FUSED_TARGET * (float)FUSED_S / (float)n));
+    const int i0 = (int)(64.0f * (1.0f - __expf(-(c0 + 1.0f) * 0.015625f)));
+    const float th = __shfl(srt, i0);
+    if (lane == 0) theta[i] = th;
+}
+
+// One wave per row: the row's list against the final prices.  The cache does not depend on the order of the list.
+__global__ __launch_bounds__(256) void fused_fixup(int n, const float *__restrict__ v, const float *__restrict__ theta,
+                                                   const int32_t *__restrict__ cnt, const uint2 *__restrict__ list,
+                                                   const int32_t *__restrict__ same_prev, uint32_t *__restrict__ cache_col,
+                                                   float *__restrict__ cache_val, int32_t *__restrict__ rowlist, int32_t *__restrict__ nfail,
+                                                   int min_kept) {
+    constexpr int NT = COLRED_CAP / 64;
+    __shared__ uint32_t s_col[4][KC];
+    __shared__ float s_val[4][KC];
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int i = (int)blockIdx.x * 4 + w;
+    if (i >= n) return;
+    if (same_prev && same_prev[i]) return;                                // a copy of the previous row: replicate_group_caches
+    const int c = __builtin_amdgcn_readfirstlane(cnt[i]);
+    const uint64_t lt = (1ull << lane) - 1ull;
+    float tau = theta[i];
+    bool fail = c > COLRED_CAP;
+    int kept = 0;
+    if (!fail) {
+        const int nt = (c + 63) >> 6;
+        uint32_t col[NT]; float raw[NT], h[NT];
+        int below = 0;
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+            col[t] = 0; raw[t] = 0.0f; h[t] = INFINITY;
+            if (t < nt) {
+                const int k = 64 * t + lane;
+                if (k < c) {
+                    const uint2 e = list[(int64_t)i * COLRED_CAP + k];
+                    col[t] = e.x; raw[t] = __uint_as_float(e.y);
+                    const float hh = raw[t] - v[e.x];
+                    if (hh < tau) h[t] = hh;
+                }
+                below += __popcll(__ballot(h[t] < INFINITY));
+            }
+        }
+        if (below > KCU) {
+            // the 64th smallest reduced cost, as an ordered key: the largest P with at most 63 keys below it
+            uint32_t key[NT];
+#pragma unroll
+            for (int t = 0; t < NT; t++) key[t] = f2ord(h[t]);
+            uint32_t P = 0;
+            for (int bit = 31; bit >= 0; bit--) {
+                const uint32_t cand = P | (1u << bit);
+                int lower = 0;
+#pragma unroll
+                for (int t = 0; t < NT; t++) if (t < nt) lower += __popcll(__ballot(key[t] < cand));
+                if (lower <= KCU) P = cand;
+            }
+            tau = ord2f(P);
+        }
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+            if (t < nt) {
+                const bool keep = h[t] < tau;                               // (strict: ties at tau leave fewer than 63)
+                const uint64_t m = __ballot(keep);
+                if (keep) { const int p = kept + __popcll(m & lt); s_col[w][p] = col[t]; s_val[w][p] = raw[t]; }
+                kept += __popcll(m);
+            }
+        }
+        fail = kept < min_kept && n > 16;
+    }
+    if (fail) {
+        if (lane == 0) rowlist[atomicAdd(nfail, 1)] = i;
+        return;
+    }
+    // the kept columns, sorted by column (unused slots last), the floor in slot 63: the layout build_row_caches_wave leaves
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    uint32_t kc = lane < kept ? s_col[w][lane] : COLSENT;
+    float kv = lane < kept ? s_val[w][lane] : 0.0f;
+#pragma unroll
+    for (int k = 2; k <= 64; k <<= 1) {
+#pragma unroll
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            const uint32_t pk = (uint32_t)__shfl_xor((int)kc, j);
+            const float pv = __shfl_xor(kv, j);
+            const bool take_min = ((lane & j) == 0) == ((lane & k) == 0);
+            const bool sw = take_min ? (pk < kc) : (pk > kc);
+            kc = sw ? pk : kc; kv = sw ? pv : kv;
+        }
+    }
+    if (lane == KCU) { kc = COLSENT; kv = tau; }
+    cache_col[(int64_t)i * KC + lane] = kc;
+    cache_val[(int64_t)i * KC + lane] = kv;
 }
 
 // Argument block of one problem (kernels get an array of them: one workgroup per problem).  Fields through an X-macro because
@@ -2175,6 +2405,10 @@ int check_opts(const cyto_lap_opts &o) {
     return CYTO_OK;
 }
 
+// process-wide: solves whose first caches came from the column reduction's pass, and the rows of those solves that the row builder
+// swept all the same (every row of a solve that gave the lists up)
+static std::atomic<long long> g_fused_solves{0}, g_fused_fallback_rows{0};
+
 // ---- float32: one problem of a batch (all problems of a batch have the same n) ----
 struct F32Job {
     // in
@@ -2191,6 +2425,9 @@ struct F32Job {
     int nused = 0;
     const float *dcost = nullptr; int64_t dld = 0;
     int h_nonfinite = 0, h_ngroups = 0;
+    // first caches from the column reduction's pass (fused_*): w | theta | cnt | rowlist | nfail views into the slab, the lists behind them
+    bool fused = false; int h_fused_failed = 0;
+    float *f_w = nullptr, *f_theta = nullptr; int32_t *f_cnt = nullptr, *f_rows = nullptr, *f_nfail = nullptr; uint2 *f_list = nullptr;
     LapStatus h_hand = {};      // numfree .. lazy_done, when jv_aug_lazy may have given up
     Chain2Args c2; LazyArgs la;
     size_t shm_lazy = 0, shm_aug = 0;
@@ -2208,15 +2445,16 @@ struct F32Plan {            // what depends on n (and the options) only: identic
 };
 
 int build_caches(const CachePlan &cp, int n, int64_t ld, const float *cost, const int32_t *rowmap, const float *v, uint32_t *cache_col,
-                 float *cache_val, const int32_t *same, hipStream_t stream) {
-    // (a wave per row; the grid: cp.waves waves on every CU, four to a workgroup)
-    const int g = std::max(1, std::min((n + CBW - 1) / CBW, cp.waves * cp.cus / CBW));
-    if (cp.unroll == 8)
+                 float *cache_val, const int32_t *same, hipStream_t stream, const int32_t *rowlist, int count) {
+    // (a wave per row; the grid: cp.waves waves on every CU, four to a workgroup; rowlist: only those `count` rows, or null: all)
+    const int nrows = rowlist ? count : n;
+    const int g = std::max(1, std::min((nrows + CBW - 1) / CBW, cp.waves * cp.cus / CBW));
+    if (nrows > 0 && cp.unroll == 8)                                   // (an empty list: only the runs of identical rows are copied)
         hipLaunchKernelGGL(build_row_caches_wave<8>, dim3(g), dim3(64 * CBW), 0, stream, n, ld, cost, v, cache_col, cache_val, rowmap, same,
-                           cp.stream);
-    else
+                           cp.stream, rowlist, count);
+    else if (nrows > 0)
         hipLaunchKernelGGL(build_row_caches_wave<4>, dim3(g), dim3(64 * CBW), 0, stream, n, ld, cost, v, cache_col, cache_val, rowmap, same,
-                           cp.stream);
+                           cp.stream, rowlist, count);
     // (runs of identical rows: one cache per run, copied to the rest)
     if (same)
         hipLaunchKernelGGL(replicate_group_caches, dim3(std::max(1, std::min((n + 3) / 4, 2048))), dim3(256), 0, stream, n, same, cache_col,
@@ -2390,6 +2628,15 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
     pl.shm_chain = pl.lds_variant ? (((size_t)npad * 6 + 15) / 16) * 16 : (cs_lds_chain ? (((size_t)npad * 2 + 15) / 16) * 16 : 16);
 
     const size_t nT = (size_t)n * sizeof(float), nI = (size_t)n * sizeof(int32_t);
+    // First caches from the column reduction's pass (fused_*, above): one float32 problem per call on the wide solver, no row map, the
+    // streaming builder's contract (cache_stream != -1), from 32 768 rows on.  A few-cell-type matrix gives the lists up (its sampled
+    // minima lie far above the final ones) and has paid the sample and the appends for nothing: 27.29 -> 27.72 ms at 20 000^2, more
+    // than that leg's spread, so the gate starts above it.
+    // (developer knob, read once per process: CYTO_CACHE_FUSED = 1 or unset: as above; 0: never; 2: from 2 048 rows on -- the tests)
+    const int fused_knob = CYTO_KNOB("CYTO_CACHE_FUSED").set ? CYTO_KNOB("CYTO_CACHE_FUSED").value : 1;
+    const bool fused_gate = fused_knob != 0 && nb == 1 && pl.wide && !jobs[0].rowmap_host && pl.cache.stream == 1 &&
+                            n >= (fused_knob >= 2 ? FUSED_S : 32768);
+    const int fused_rs = std::min(1024, n / 2);                   // rows sampled for w
     // ---- stage 1 (every problem, back to back on the stream: full-chip streaming kernels): column reduction, row groups ----
     CYTO_HIP(hipEventRecord(e0, stream));
     for (F32Job &j : jobs) {
@@ -2427,19 +2674,31 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
             CYTO_HIP(hipMemcpyAsync(j.b_ufirst.p, ufirst.data(), (size_t)j.nused * 4, hipMemcpyHostToDevice, stream));
             CYTO_HIP(hipStreamSynchronize(stream));       // ulist / ufirst are locals
         }
-        // workspace (blocks of the device cache: no hipMalloc / hipFree once a size has been seen)
-        {
+        // workspace (blocks of the device cache: no hipMalloc / hipFree once a size has been seen).  The candidate lists are the one
+        // large part (n x 4 KB: 205 MB at n = 50 000): where the block with them cannot be had, the solve runs without them
+        j.fused = fused_gate;
+        for (;;) {
             size_t off = 0;
             auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
             const size_t o_fws = take(6 * nT + 64), o_iws = take(10 * nI + 64), o_imin = take(nI), o_pmin = take((size_t)pl.rowblocks * nT),
                          o_parg = take((size_t)pl.rowblocks * nI), o_misc = take(sizeof(LapStatus)), o_same = take(nI), o_gid = take(nI),
                          o_ccol = take((size_t)n * KC * sizeof(uint32_t)), o_cval = take((size_t)n * KC * sizeof(float));
-            if ((rc = j.slab.alloc(off, stream))) return rc;
+            const size_t o_fw = j.fused ? take(nT + 16) : 0, o_fth = j.fused ? take(nT) : 0, o_fcnt = j.fused ? take(nI + 256) : 0,
+                         o_frows = j.fused ? take(nI) : 0, o_flist = j.fused ? take((size_t)n * COLRED_CAP * sizeof(uint2)) : 0;
+            rc = j.slab.alloc(off, stream);
+            if (rc == CYTO_ERR_NOMEM && j.fused) { (void)hipGetLastError(); j.fused = false; continue; }      // (the failed hipMalloc's error is not the solve's)
+            if (rc) return rc;
             char *base = j.slab.as<char>();
+            if (j.fused) {
+                j.f_w = reinterpret_cast<float *>(base + o_fw); j.f_theta = reinterpret_cast<float *>(base + o_fth);
+                j.f_cnt = reinterpret_cast<int32_t *>(base + o_fcnt); j.f_nfail = j.f_cnt + n;      // (one memset clears both)
+                j.f_rows = reinterpret_cast<int32_t *>(base + o_frows); j.f_list = reinterpret_cast<uint2 *>(base + o_flist);
+            }
             j.b_fws.view(base + o_fws, stream); j.b_iws.view(base + o_iws, stream); j.b_imin.view(base + o_imin, stream);
             j.b_pmin.view(base + o_pmin, stream); j.b_parg.view(base + o_parg, stream); j.b_misc.view(base + o_misc, stream);
             j.b_same.view(base + o_same, stream); j.b_gid.view(base + o_gid, stream); j.b_ccol.view(base + o_ccol, stream);
             j.b_cval.view(base + o_cval, stream);
+            break;
         }
         // float workspace: v | u | ... ; int workspace: rowsol | colsol | matches | freerows | rtrows | pred | ...
         float *d_v = j.b_fws.as<float>();
@@ -2451,6 +2710,21 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
             const int nrows = j.rowmap_host ? j.nused : n;
             const int rpb = j.rowmap_host ? (nrows + pl.rowblocks - 1) / pl.rowblocks : pl.rows_per_block;
             const int rblocks = j.rowmap_host ? (nrows + rpb - 1) / rpb : pl.rowblocks;
+            if (j.fused) {
+                // w from the first rows (the partial minima go through pmin / parg, which the full pass then overwrites), theta, and
+                // the full pass with appends
+                const int srb0 = std::max(1, std::min(pl.rowblocks, (fused_rs + 15) / 16)), srpb = (fused_rs + srb0 - 1) / srb0,
+                          srb = (fused_rs + srpb - 1) / srpb;
+                hipLaunchKernelGGL(colred_partial<float>, dim3(pl.colblocks, srb), dim3(256), 0, stream, n, j.dld, j.dcost, srpb,
+                                   j.b_pmin.as<float>(), j.b_parg.as<int32_t>(), &j.st()->nonfinite, fused_rs, (const int32_t *)nullptr,
+                                   (const int32_t *)nullptr);
+                hipLaunchKernelGGL(fused_w, dim3((n + 255) / 256), dim3(256), 0, stream, n, srb, j.b_pmin.as<float>(), j.f_w);
+                hipLaunchKernelGGL(fused_theta, dim3((n + 3) / 4), dim3(256), 0, stream, n, j.dld, j.dcost, j.f_w, j.f_theta);
+                CYTO_HIP(hipMemsetAsync(j.f_cnt, 0, nI + sizeof(int32_t), stream));
+                const ColredAppend ap = {j.f_w, j.f_theta, j.f_cnt, j.f_list};
+                hipLaunchKernelGGL(colred_partial_append, dim3(pl.colblocks, rblocks), dim3(256), 0, stream, n, j.dld, j.dcost, rpb,
+                                   j.b_pmin.as<float>(), j.b_parg.as<int32_t>(), &j.st()->nonfinite, nrows, ap);
+            } else
             hipLaunchKernelGGL(colred_partial<float>, dim3(pl.colblocks, rblocks), dim3(256), 0, stream, n, j.dld, j.dcost, rpb,
                                j.b_pmin.as<float>(), j.b_parg.as<int32_t>(), &j.st()->nonfinite, nrows,
                                j.rowmap_host ? j.b_ulist.as<int32_t>() : (const int32_t *)nullptr,
@@ -2474,6 +2748,11 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
                 hipLaunchKernelGGL(rows_same_as_prev<float>, dim3(min(n, 2048)), dim3(256), 0, stream, n, j.dld, j.dcost, j.b_same.as<int32_t>());
             hipLaunchKernelGGL(rows_group_ids, dim3(1), dim3(1024), 0, stream, n, j.b_same.as<int32_t>(), j.b_gid.as<int32_t>(),
                                &j.st()->ngroups);
+        }
+        if (j.fused) {                                             // the lists against the final prices; what fails goes on f_rows
+            hipLaunchKernelGGL(fused_fixup, dim3((n + 3) / 4), dim3(256), 0, stream, n, j.b_fws.as<float>(), j.f_theta, j.f_cnt, j.f_list,
+                               j.b_same.as<int32_t>(), j.b_ccol.as<uint32_t>(), j.b_cval.as<float>(), j.f_rows, j.f_nfail, fused_min_kept(n));
+            CYTO_HIP(hipMemcpyAsync(&j.h_fused_failed, j.f_nfail, sizeof(int), hipMemcpyDeviceToHost, stream));
         }
         // a non-finite cost makes every later comparison meaningless: that problem stops before the chain
         CYTO_HIP(hipMemcpyAsync(&j.h_nonfinite, &j.st()->nonfinite, sizeof(int), hipMemcpyDeviceToHost, stream));
@@ -2549,6 +2828,15 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
             if (j.alive())
                 wj.push_back({j.dcost, j.dld, j.rowmap(), j.b_fws.as<float>(), j.b_iws.as<int32_t>(), j.b_ccol.as<uint32_t>(),
                               j.b_cval.as<float>(), j.b_misc.as<char>(), j.same(n), j.h_ngroups, &j.b_wide});
+        if (jobs[0].fused && !wj.empty()) {
+            // few enough rows failed: the row builder takes those alone; otherwise (a few-cell-type matrix: the sampled minima lie too
+            // far above the final ones) it builds every row as if there had been no lists
+            F32Job &j = jobs[0];
+            if (j.h_fused_failed <= n / 8) { wj[0].first_rows = j.f_rows; wj[0].first_count = j.h_fused_failed; }
+            else j.h_fused_failed = n;
+            g_fused_solves.fetch_add(1);
+            g_fused_fallback_rows.fetch_add(j.h_fused_failed);
+        }
         rc = wide_solve_batch(wp, wj, stream, e1c, e1d);
     } else if (opts.chain_variant >= 2) rc = launch_batch<0, false>(pl, jobs, stream, e1c, e1d, d_c2, d_la);
     else if (pl.force_l2 && n <= 5 * per2) rc = launch_batch<5, false>(pl, jobs, stream, e1c, e1d, d_c2, d_la);
@@ -2607,7 +2895,7 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
             info->ms_colred = ms_colred; info->ms_cache = ms_cache; info->ms_chain = ms_chain; info->ms_arr = ms_arr; info->ms_aug = ms_aug;
             info->ms_total = info->ms_colred + info->ms_cache + info->ms_chain;
             info_from_counters(info, n, h);
-            info->hbm_row_reads = 2 * (int64_t)n + h.counters[C_ROWS_READ];
+            info->hbm_row_reads = (j.fused ? (int64_t)n + fused_rs + j.h_fused_failed : 2 * (int64_t)n) + h.counters[C_ROWS_READ];
             info->dense_refreshes = h.counters[C2_DENSE_REFRESH];
             info->aug_scans_skipped = h.counters[C2_AUG_SKIPPED];
             info->aug_dense_scans = h.counters[C2_AUG_DENSE];
@@ -2758,5 +3046,8 @@ int cyto_lap_f64_opts(int n, const double *cost, int64_t ld, int cost_on_device,
                       double *u, double *v, double *total, cyto_lap_info *info, int device_id, void *stream, const cyto_lap_opts *opts) {
     return cyto::lap_solve_f64(n, cost, ld, cost_on_device, rowsol, colsol, u, v, total, info, device_id, reinterpret_cast<hipStream_t>(stream), opts ? *opts : cyto::k_default_opts);
 }
+
+long long cyto_fused_cache_solves(void) { return cyto::g_fused_solves.load(); }
+long long cyto_fused_cache_fallback_rows(void) { return cyto::g_fused_fallback_rows.load(); }
 
 }  // extern "C"

@@ -8,14 +8,15 @@ namespace cyto {
 constexpr int WIDE_PAR_GMAX = 64;      // most searches of one problem at once (cyto_lap_opts.wide_par)
 
 // The row caches of one problem against its prices v (lap_jv.hip: build_row_caches_wave, then replicate_group_caches over the runs of
-// identical rows): what both solvers start from, and what the wide solver rebuilds between its launches.
+// identical rows): what both solvers start from, and what the wide solver rebuilds between its launches.  rowlist: build only these
+// `count` rows (device memory; any order), or null: all of them.
 struct CachePlan {
     int waves = 8, unroll = 4;          // waves per CU, quads in flight per lane
     int stream = 1;                     // 1: the guess-free single sweep (cb_stream); 0: a neighbour's floor as the guess
     int cus = 256;                      // CUs of the device (device_cus)
 };
 int build_caches(const CachePlan &cp, int n, int64_t ld, const float *cost, const int32_t *rowmap, const float *v, uint32_t *cache_col,
-                 float *cache_val, const int32_t *same, hipStream_t stream);
+                 float *cache_val, const int32_t *same, hipStream_t stream, const int32_t *rowlist = nullptr, int count = 0);
 
 // One problem of a batch as the float32 driver has set it up (lap_jv.hip: F32Job, private to it, after the column reduction).  Device memory.
 struct WideJob {
@@ -28,6 +29,8 @@ struct WideJob {
     const int32_t *same;                // [n] 1 = the row equals the row before it (runs of identical rows), or null
     int ngroups;                        // runs of identical rows (n: none)
     DevBuf *state;                      // the solver's own state: allocated here
+    // the first caches came out of the column reduction's pass (lap_jv.hip: fused_fixup) but for these rows; -1: they did not, build all
+    const int32_t *first_rows = nullptr; int first_count = -1;
 };
 struct WidePlan {
     int n;

@@ -2556,7 +2556,11 @@ int wide_solve_batch(const WidePlan &pl, const std::vector<WideJob> &jobs, hipSt
         }
         return CYTO_OK;
     };
-    if ((rc = build_caches_of(nullptr))) return rc;
+    if (nl == 1 && jobs[0].first_count >= 0) {                 // the first caches exist but for the listed rows (lap_jv.hip: fused_fixup)
+        const WideJob &j = jobs[0];
+        if ((rc = build_caches(pl.cache, n, j.ld, j.cost, j.rowmap, j.fws, j.cache_col, j.cache_val, j.same, stream, j.first_rows, j.first_count)))
+            return rc;
+    } else if ((rc = build_caches_of(nullptr))) return rc;
     CYTO_HIP(hipEventRecord(ev_cache_done, stream));
     struct ParSlot { std::atomic<int> *p = nullptr; ~ParSlot() { if (p) p->store(0); } } par_slot;       // (released on every return path)
     int dev_now = 0;

@@ -42,6 +42,11 @@ int cyto_abi_sizes(size_t *lap_info, size_t *lap_opts, size_t *assign_info, size
 /* Solves of this process whose searches ran in the wide solver's embedded form (one problem, several searches at once, prices in
  * global memory: DESIGN 4.1a) -- a process-wide count, so that a test can tell which form ran; it is not part of cyto_lap_info. */
 long long cyto_wide_embedded_solves(void);
+/* Float32 solves of this process whose first row caches came from the column reduction's own pass (one problem per
+ * call, no row map, from 32 768 rows on), and the rows of those solves that the row builder swept all the same (the rows the lists
+ * could not certify; every row of a solve that gave the lists up).  Process-wide counts, for tests and tools. */
+long long cyto_fused_cache_solves(void);
+long long cyto_fused_cache_fallback_rows(void);
 
 /* ---- device + memory plumbing (so callers can keep the cost matrix resident in HBM) ---- */
 int cyto_device_count(int *count);
