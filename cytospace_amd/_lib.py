@@ -171,6 +171,8 @@ def lib():
         u32p, i32p = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32)
         L.cyto_downsample.argtypes = [i32, i32, vp, i64, i32, vp, i64, i32, i32, u32p, i32p, ctypes.POINTER(ctypes.c_int64), i32]
         L.cyto_downsample.restype = ctypes.c_int
+        L.cyto_placeholders.argtypes = [i32, i32, vp, i64, i32, i64, vp, i64, u32p, i32p, ctypes.POINTER(ctypes.c_int64), i64, i32]
+        L.cyto_placeholders.restype = ctypes.c_int
         L.cyto_mt19937_fill.argtypes = [u32p, i32p, i32, u32p, i32]
         L.cyto_mt19937_fill.restype = ctypes.c_int
         i64p = ctypes.POINTER(ctypes.c_int64)

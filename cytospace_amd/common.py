@@ -323,6 +323,65 @@ def downsample_device(data_df, target_count, device_id=0, dtype=np.int64, return
     return (df, words.value) if return_words else df
 
 
+# upload codes of cyto_placeholders; other dtypes are widened on the host first (to what numpy's float64 assignment sees anyway)
+_PH_IN = {np.dtype(np.int64): 5, np.dtype(np.uint16): 2, np.dtype(np.float64): 1}
+_PH_WIDEN = {np.dtype(t): np.int64 for t in (np.int8, np.int16, np.int32, np.uint8, np.uint32)}
+_PH_WIDEN[np.dtype(np.float32)] = np.float64
+
+
+def place_holders_device(own, short, device_id=0, return_words=False, rbuf_bytes=0):
+    """The synthetic cells of sample_single_cells' "place_holders" branch on the GPU (C ABI: cyto_placeholders): for the G x n
+    matrix `own` of a cell type's cells, the G x short float64 array of the host loop
+
+        fake[:, k] = [np.random.choice(own[g, :]) for g in range(G)]          k = 0 .. short-1
+
+    and the same global numpy RandomState afterwards (np.random.set_state keeps has_gauss and the cached value).  That loop
+    consumes the stream of np.random.randint(0, n, size=(short, G)) -- masked rejection sampling on 32-bit MT19937 words, no
+    word at all when n == 1 -- which the device reproduces word for word.
+
+    own: int64, uint16 or float64 as they are (rows may be strided); narrower integers are widened to int64 and float32 to
+    float64 first; any other dtype raises TypeError.  return_words: also return the number of raw words consumed.
+    rbuf_bytes: a cap on one block's draws (0: the library's default); results do not depend on it."""
+    out, state, words = place_holders_from_state(own, short, np.random.get_state(), device_id, rbuf_bytes)
+    np.random.set_state(state)
+    return (out, words) if return_words else out
+
+
+def place_holders_from_state(own, short, state, device_id=0, rbuf_bytes=0):
+    """place_holders_device on an explicit legacy state tuple (np.random.get_state()) instead of numpy's global one: returns
+    (the G x short array, the state after the draws, words consumed).  Touches nothing global, so host threads may call it
+    side by side, each with a state of its own."""
+    own = np.asarray(own)
+    if own.ndim != 2:
+        raise ValueError("own must be a genes x cells matrix")
+    if own.dtype in _PH_WIDEN:
+        own = own.astype(_PH_WIDEN[own.dtype])
+    if own.dtype not in _PH_IN:
+        raise TypeError(f"Cannot draw place-holder cells from values of dtype {own.dtype}")
+    short = int(short)
+    if short < 0:
+        raise ValueError("short must be non-negative")
+    G, n = own.shape
+    if n == 0 and G > 0 and short > 0:
+        raise ValueError("a cell type without cells has nothing to draw from")        # (np.random.choice([]) raises as well)
+    out = np.empty((G, short), np.float64)
+    if state[0] != "MT19937":
+        raise ValueError("numpy's global generator is not MT19937")
+    if G == 0 or short == 0:
+        return out, state, 0
+    item = own.dtype.itemsize
+    if own.strides[1] != item or own.strides[0] % item or own.strides[0] < n * item:
+        own = np.ascontiguousarray(own)
+    key = np.array(state[1], dtype=np.uint32)
+    pos = ctypes.c_int32(int(state[2]))
+    words = ctypes.c_int64()
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    _lib.check(_lib.lib().cyto_placeholders(G, n, own.ctypes.data, own.strides[0] // item, _PH_IN[own.dtype], short, out.ctypes.data,
+                                            short, key.ctypes.data_as(u32p), ctypes.byref(pos), ctypes.byref(words), int(rbuf_bytes),
+                                            device_id))
+    return out, ("MT19937", key, pos.value, state[3], state[4]), words.value
+
+
 def mt19937_fill(n, device_id=0):
     """The next n raw 32-bit words of numpy's global legacy stream, generated on the GPU (C ABI: cyto_mt19937_fill, the
     generator of downsample_device alone); numpy's global state is advanced past them, as

@@ -16,6 +16,9 @@
 //
 // Columns that are not downsampled are copied by ds_copy.  Cells are processed in blocks whose r rows fit in ~1 GiB; stage 1
 // of block b+1 (its own stream) overlaps stage 2 of block b (double-buffered rbuf).
+//
+// cyto_placeholders (the "place_holders" sampler's synthetic cells) runs the same stage 1 -- a synthetic cell is a "cell" with
+// range n - 1 and G accepted draws -- with ph_gather as its stage 2.
 #include "cyto_common.h"
 
 #include <algorithm>
@@ -220,6 +223,37 @@ __global__ __launch_bounds__(HIST_T) void ds_hist(const TIn *x, int64_t ldx, int
     }
 }
 
+// Place-holder cells (cyto_placeholders), stage 2: the draws of a block of nk synthetic cells arrive cell-major from ds_stream,
+// r[k * G + g] in [0, n), and select out[g][k0 + k] = own[g][r].  A 64 (genes) x 64 (cells) tile of r goes through LDS (rows
+// padded to 65 words: the column read is conflict-free), so r is read along g and out is written along k; a wave's 64 gathers
+// then fall into ONE row of own.  r == nullptr (n == 1): every cell is own's single column.  Tiles: blockIdx.x = kt * gtiles + gt.
+constexpr int PH_TILE = 64, PH_T = 256;
+template <typename TIn>
+__global__ __launch_bounds__(PH_T) void ph_gather(const TIn *own, int64_t ld_own, int G, int n, const uint32_t *r, int nk, double *out,
+                                                  int64_t ldo, int64_t k0, unsigned gtiles) {
+    __shared__ uint32_t tile[PH_TILE][PH_TILE + 1];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int64_t gb = (int64_t)(blockIdx.x % gtiles) * PH_TILE;
+    const int kb = (int)(blockIdx.x / gtiles) * PH_TILE;
+    if (r) {
+        const int64_t g = gb + tx;
+        for (int kk = ty; kk < PH_TILE; kk += PH_T / 64) {
+            const int k = kb + kk;
+            if (k < nk && g < G) tile[kk][tx] = r[(size_t)k * (size_t)G + (size_t)g];
+        }
+        __syncthreads();
+    }
+    const int k = kb + tx;
+    if (k >= nk) return;
+    const uint32_t last = (uint32_t)(n - 1);
+    for (int gg = ty; gg < PH_TILE; gg += PH_T / 64) {
+        const int64_t g = gb + gg;
+        if (g >= G) break;
+        const uint32_t j = r ? min(tile[tx][gg], last) : 0u;         // (ds_stream accepts r <= n - 1 only)
+        out[(size_t)g * (size_t)ldo + (size_t)(k0 + k)] = (double)own[(size_t)g * (size_t)ld_own + j];
+    }
+}
+
 // (Mem, cyto_common.h: these buffers are as large as the count matrix and do not go through the block cache)
 
 size_t dtype_size(int code) {
@@ -277,6 +311,25 @@ int dispatch(int in_code, int out_code, const void *x, int64_t ldx, int G, int C
     if (out_code == CYTO_DTYPE_U16)
         return dispatch_in<uint16_t>(in_code, x, ldx, G, C, is_ds, out, ldo, s, nd, cells, rbuf, target, copy);
     return dispatch_in<int64_t>(in_code, x, ldx, G, C, is_ds, out, ldo, s, nd, cells, rbuf, target, copy);
+}
+
+template <typename TIn>
+int launch_gather(const void *own, int64_t ld_own, int G, int n, const uint32_t *r, int nk, double *out, int64_t ldo, int64_t k0,
+                  hipStream_t s) {
+    const unsigned gtiles = (unsigned)((G + PH_TILE - 1) / PH_TILE), ktiles = (unsigned)((nk + PH_TILE - 1) / PH_TILE);
+    hipLaunchKernelGGL(ph_gather<TIn>, dim3(gtiles * ktiles), dim3(PH_T), 0, s, (const TIn *)own, ld_own, G, n, r, nk, out, ldo, k0,
+                       gtiles);
+    CYTO_HIP(hipGetLastError());
+    return CYTO_OK;
+}
+
+int dispatch_gather(int code, const void *own, int64_t ld_own, int G, int n, const uint32_t *r, int nk, double *out, int64_t ldo,
+                    int64_t k0, hipStream_t s) {
+    switch (code) {
+        case CYTO_DTYPE_U16: return launch_gather<uint16_t>(own, ld_own, G, n, r, nk, out, ldo, k0, s);
+        case CYTO_DTYPE_F64: return launch_gather<double>(own, ld_own, G, n, r, nk, out, ldo, k0, s);
+        default: return launch_gather<int64_t>(own, ld_own, G, n, r, nk, out, ldo, k0, s);
+    }
 }
 
 // accepted draws of one block of cells: 1 GiB (CYTO_DS_RBUF_BYTES: smaller blocks, for tests of the block hand-over)
@@ -379,6 +432,70 @@ int cyto_downsample(int G, int C, const void *x, int64_t ldx, int x_dtype, void 
     }
     CYTO_HIP(hipMemcpy2DAsync(out, (size_t)ldo * out_sz, dout.p, (size_t)C * out_sz, (size_t)C * out_sz, (size_t)G, hipMemcpyDeviceToHost,
                               sa.s));
+    CYTO_HIP(hipStreamSynchronize(sa.s));
+    memcpy(key, hs.key, sizeof hs.key);
+    *pos = (int32_t)hs.pos;
+    if (words_out) *words_out = (int64_t)hs.words;
+    return CYTO_OK;
+}
+
+int cyto_placeholders(int G, int n, const void *own, int64_t ld_own, int own_dtype, int64_t short_count, double *out, int64_t ldo,
+                      uint32_t *key, int32_t *pos, int64_t *words_out, int64_t cap_bytes, int device_id) {
+    if (G <= 0 || n <= 0 || short_count < 0 || !own || !out || !key || !pos || ld_own < n || ldo < short_count || cap_bytes < 0)
+        return CYTO_ERR_BAD_ARG;
+    const size_t in_sz = own_dtype == CYTO_DTYPE_U16 ? 2 : own_dtype == CYTO_DTYPE_I64 || own_dtype == CYTO_DTYPE_F64 ? 8 : 0;
+    if (!in_sz) return CYTO_ERR_BAD_ARG;
+    MtState hs;
+    int rc = load_state(hs, key, pos);
+    if (rc) return rc;
+    if (words_out) *words_out = 0;
+    if (short_count == 0) return CYTO_OK;
+    if ((rc = select_device(device_id))) return rc;
+    // a block's draws: at most the cap (never above the default, which also bounds a launch's tiles), at least one cell
+    const size_t cap = cap_bytes ? std::min((size_t)cap_bytes, rbuf_bytes()) : rbuf_bytes();
+    const int64_t per = std::max<int64_t>(1, std::min<int64_t>(short_count, (int64_t)(cap / ((size_t)G * 4))));
+    const int64_t nblocks = (short_count + per - 1) / per;
+    const bool draw = n > 1;                             // randint(0, 1) takes no word
+    Mem down, dout, dstate, drng, drbuf;                 // (declared before the streams, as in cyto_downsample)
+    StreamGuard sa, sb;                                  // sa: upload, stage 2, download; sb: stage 1
+    if ((rc = sa.acquire()) || (rc = sb.acquire())) return rc;
+    if ((rc = down.alloc((size_t)G * n * in_sz)) || (rc = dout.alloc((size_t)G * (size_t)short_count * 8))) return rc;
+    CYTO_HIP(hipMemcpy2DAsync(down.p, (size_t)n * in_sz, own, (size_t)ld_own * in_sz, (size_t)n * in_sz, (size_t)G, hipMemcpyHostToDevice,
+                              sa.s));
+    if (!draw) {
+        for (int64_t b = 0; b < nblocks; b++) {
+            const int64_t k0 = b * per;
+            if ((rc = dispatch_gather(own_dtype, down.p, n, G, n, nullptr, (int)std::min(per, short_count - k0), dout.as<double>(),
+                                      short_count, k0, sa.s)))
+                return rc;
+        }
+    } else {
+        if ((rc = dstate.alloc(sizeof(MtState))) || (rc = drng.alloc((size_t)per * 4)) ||
+            (rc = drbuf.alloc((size_t)std::min<int64_t>(nblocks, 2) * (size_t)per * (size_t)G * 4)))
+            return rc;
+        CYTO_HIP(hipMemsetD32Async((hipDeviceptr_t)drng.p, n - 1, (size_t)per, sa.s));       // every synthetic cell draws below n
+        CYTO_HIP(hipMemcpyAsync(dstate.p, &hs, sizeof hs, hipMemcpyHostToDevice, sa.s));
+        Events<5> ev;                                   // 0: inputs ready; 1,2: stage 1 of buffer 0/1 done; 3,4: stage 2 of it done
+        if ((rc = ev.create())) return rc;
+        CYTO_HIP(hipEventRecord(ev[0], sa.s));
+        CYTO_HIP(hipStreamWaitEvent(sb.s, ev[0], 0));
+        for (int64_t b = 0; b < nblocks; b++) {
+            const int64_t k0 = b * per;
+            const int nk = (int)std::min(per, short_count - k0), buf = (int)(b & 1);
+            uint32_t *rb = drbuf.as<uint32_t>() + (size_t)buf * (size_t)per * (size_t)G;
+            if (b >= 2) CYTO_HIP(hipStreamWaitEvent(sb.s, ev[3 + buf], 0));
+            hipLaunchKernelGGL(ds_stream, dim3(1), dim3(64), 0, sb.s, dstate.as<MtState>(), drng.as<uint32_t>(), nk, G, rb);
+            CYTO_HIP(hipGetLastError());
+            CYTO_HIP(hipEventRecord(ev[1 + buf], sb.s));
+            CYTO_HIP(hipStreamWaitEvent(sa.s, ev[1 + buf], 0));
+            if ((rc = dispatch_gather(own_dtype, down.p, n, G, n, rb, nk, dout.as<double>(), short_count, k0, sa.s))) return rc;
+            CYTO_HIP(hipEventRecord(ev[3 + buf], sa.s));
+        }
+        CYTO_HIP(hipStreamSynchronize(sb.s));
+        CYTO_HIP(hipMemcpyAsync(&hs, dstate.p, sizeof hs, hipMemcpyDeviceToHost, sa.s));
+    }
+    CYTO_HIP(hipMemcpy2DAsync(out, (size_t)ldo * 8, dout.p, (size_t)short_count * 8, (size_t)short_count * 8, (size_t)G,
+                              hipMemcpyDeviceToHost, sa.s));
     CYTO_HIP(hipStreamSynchronize(sa.s));
     memcpy(key, hs.key, sizeof hs.key);
     *pos = (int32_t)hs.pos;

@@ -596,6 +596,31 @@ def sample_single_cells(scRNA_data, cell_type_data, cell_type_numbers_int, sampl
     `np.random.choice` with replacement ("duplicates") or synthetic cells whose genes are drawn independently from
     the type's cells ("place_holders").  Both generators are seeded with `seed` first, and are consumed in the
     reference's order, so the same seed reproduces the reference's sample."""
+    return _sample_single_cells(scRNA_data, cell_type_data, cell_type_numbers_int, sampling_method, seed, _place_holders_host)
+
+
+def sample_single_cells_device(scRNA_data, cell_type_data, cell_type_numbers_int, sampling_method, seed, device_id=0):
+    """sample_single_cells with the synthetic cells of "place_holders" drawn on GPU device_id (common.place_holders_device):
+    the same DataFrame -- index, column names, dtypes, values -- and the same states of numpy's global generator and of
+    python's `random` afterwards.  Everything else (random.sample, "duplicates", the order of types, the errors) is the
+    host code of sample_single_cells."""
+    from .common import place_holders_device
+    return _sample_single_cells(scRNA_data, cell_type_data, cell_type_numbers_int, sampling_method, seed,
+                                lambda own, short: place_holders_device(own, short, device_id=device_id))
+
+
+def _place_holders_host(own, short):
+    """`short` synthetic cells of a type whose cells are the columns of `own`: every gene drawn independently from the
+    type's values of that gene, one np.random.choice per (cell, gene) as in the reference."""
+    fake = np.zeros((own.shape[0], short))
+    for k in range(short):
+        fake[:, k] = [np.random.choice(own[g, :]) for g in range(own.shape[0])]
+    return fake
+
+
+def _sample_single_cells(scRNA_data, cell_type_data, cell_type_numbers_int, sampling_method, seed, place_holders):
+    """The sampler behind sample_single_cells and sample_single_cells_device; place_holders(own, short) makes the
+    genes x short float64 block of synthetic cells from numpy's global generator."""
     import random
     import pandas as pd
     if sampling_method not in ("duplicates", "place_holders"):
@@ -622,9 +647,7 @@ def sample_single_cells(scRNA_data, cell_type_data, cell_type_numbers_int, sampl
         else:
             own = scRNA_data.iloc[:, members].to_numpy()
             np.random.choice(members, short)          # (the reference draws and discards this)
-            fake = np.zeros((own.shape[0], short))
-            for k in range(short):
-                fake[:, k] = [np.random.choice(own[g, :]) for g in range(own.shape[0])]
+            fake = place_holders(own, short)
             names.append(np.array(ids[members]))
             names.append(np.array([cell_type.replace('TYPE_', 'CELL_') + '_new_' + str(k + 1) for k in range(short)]))
             blocks.append(own); blocks.append(fake)
@@ -739,7 +762,8 @@ def main_cytospace(scRNA_path, cell_type_path,
                    plot_off=False, geometry="honeycomb", max_num_cells_plot=50000, num_column=3, devices=None):
     """cytospace.py:472-717 with the same arguments (plus `devices`, see apply_linear_assignment) and the same random-number
     use: both generators seeded, then cells per spot, cell type numbers, the gene intersection, the downsampling (on the GPU,
-    the same draws as the host's), sample_single_cells and the partitions; then every chunk on the GPU solver and the
+    the same draws as the host's), sample_single_cells (its place-holder cells drawn on the GPU, again the host's draws) and the
+    partitions; then every chunk on the GPU solver and the
     reference's output files and log.  Plots are not produced (the plotting arguments are accepted and logged)."""
     import random
     import pandas as pd
@@ -813,7 +837,8 @@ def main_cytospace(scRNA_path, cell_type_path,
     log("Number of genes used for mapping: " + str(len(intersect_genes)) + "\n")
     log("Number of spots satisfying input for mapping: " + str(st_data.shape[1]) + "\n")
     log("Number of cells satisfying input for mapping: " + str(scRNA_data_sampled.shape[1]) + "\n")
-    scRNA_data_sampled = sample_single_cells(scRNA_data_sampled, cell_type_data, cell_type_numbers_int, sampling_method, seed)
+    scRNA_data_sampled = sample_single_cells_device(scRNA_data_sampled, cell_type_data, cell_type_numbers_int, sampling_method, seed,
+                                                    device_id=device)
     print(f"Time to down/up sample scRNA-seq data: {round(time.perf_counter() - t0, 2)} seconds")
 
     n_cells = scRNA_data_sampled.shape[1]

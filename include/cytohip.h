@@ -451,6 +451,18 @@ int cyto_assign_metric_ex(int metric, int G, const cyto_matrix *sc, int C, const
  * downsampled cell with T > 2^32 when target > 0 (numpy draws 64-bit words there), a bad dtype or size. */
 int cyto_downsample(int G, int C, const void *x, int64_t ldx, int x_dtype, void *out, int64_t ldo, int out_dtype, int target,
                     uint32_t *key, int32_t *pos, int64_t *words_out, int device_id);
+/* ---- place-holder cells (cytospace/cytospace.py:212-301, sampling_method "place_holders"): short_count synthetic cells of a cell
+ * type with n cells, gene g of each drawn independently from the type's n values of that gene -- the reference's
+ * fake[:, k] = [np.random.choice(own[g, :]) for g in range(G)], k = 0 .. short_count-1, with exactly the words numpy's legacy global
+ * RandomState would use: per (cell, gene), in that order, 32-bit words w until (w & mask) <= n-1, and NO word when n == 1.
+ * own: G x n host matrix (ld_own >= n) of CYTO_DTYPE_I64 / _U16 / _F64; out: G x short_count host float64 (ldo >= short_count),
+ * out[g][k] = (double) own[g][draw(k, g)] (the plain cast, round to nearest).  key[624] / *pos / *words_out: as in cyto_downsample.
+ * rbuf_bytes: 0, or a cap on the draws of one block of synthetic cells (at most the library's default; at least one cell per block):
+ * results never depend on it (tests force many blocks at small sizes with it).
+ * CYTO_ERR_BAD_ARG, before the device is selected: G <= 0, n <= 0, short_count < 0, a null pointer, ld_own < n, ldo < short_count, another
+ * dtype, rbuf_bytes < 0, *pos outside [0, 624].  short_count == 0: CYTO_OK, out and the state untouched. */
+int cyto_placeholders(int G, int n, const void *own, int64_t ld_own, int own_dtype, int64_t short_count, double *out, int64_t ldo,
+                      uint32_t *key, int32_t *pos, int64_t *words_out, int64_t rbuf_bytes, int device_id);
 /* The generator alone (a test hook): the next n raw 32-bit MT19937 words from (key, *pos), with the state after them. */
 int cyto_mt19937_fill(uint32_t *key, int32_t *pos, int n, uint32_t *words, int device_id);
 
