@@ -133,6 +133,14 @@ def lib():
                 getattr(L, name).restype = ctypes.c_longlong
         L.cyto_trim_device_cache.argtypes = [i32]
         L.cyto_trim_device_cache.restype = ctypes.c_int
+        if hasattr(L, "cyto_cache_poison"):                  # (absent from older A/B builds loaded through CYTOHIP_LIB)
+            L.cyto_cache_poison.argtypes = [i32]
+            L.cyto_cache_poison.restype = ctypes.c_int
+            for name in ("cyto_cache_poison_fills", "cyto_cache_poison_bytes"):
+                getattr(L, name).argtypes = []
+                getattr(L, name).restype = ctypes.c_longlong
+            L.cyto_cache_peek.argtypes = [ctypes.c_size_t, vp, i32]
+            L.cyto_cache_peek.restype = ctypes.c_int
         dp = ctypes.POINTER(ctypes.c_double)
         L.cyto_lap_f32_from_f64.argtypes = [i32, vp, i64, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_double),
                                             ctypes.POINTER(LapInfo), i32, vp]
@@ -243,6 +251,31 @@ def fused_cache_fallback_rows():
 def wide_embedded_solves():
     """Solves of this process whose searches ran in the wide solver's embedded form (cyto_wide_embedded_solves)."""
     return int(lib().cyto_wide_embedded_solves())
+
+
+def cache_poison(byte):
+    """Test hook (cyto_cache_poison): fill every work buffer handed out with `byte` (0...255); -1 or None turns it off."""
+    check(lib().cyto_cache_poison(-1 if byte is None else int(byte)))
+
+
+def cache_poison_fills():
+    return int(lib().cyto_cache_poison_fills())
+
+
+def cache_poison_bytes():
+    return int(lib().cyto_cache_poison_bytes())
+
+
+def cache_peek(nbytes, device_id=0):
+    """The first nbytes of a block of that size as the block cache hands it out (cyto_cache_peek), as a uint8 array."""
+    import numpy as np
+    out = np.empty(int(nbytes), np.uint8)
+    check(lib().cyto_cache_peek(int(nbytes), out.ctypes.data, device_id))
+    return out
+
+
+def trim_device_cache(device_id=0):
+    check(lib().cyto_trim_device_cache(device_id))
 
 
 def device_count():

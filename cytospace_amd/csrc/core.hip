@@ -2,6 +2,7 @@
 #include "cyto_common.h"
 #include <stdlib.h>
 #include <algorithm>
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <set>
@@ -73,6 +74,10 @@ size_t round_size(size_t b) {
     return (b + step - 1) / step * step;
 }
 
+// the poison hook (cyto_cache_poison): -1 off, else the byte every block handed out is filled with
+std::atomic<int> g_poison_byte{-1};
+std::atomic<long long> g_poison_fills{0}, g_poison_bytes{0};
+
 void trim_locked(DeviceCache &c) {
     for (auto &kv : c.free_blocks) { c.live.erase(kv.second); (void)hipFree(kv.second); }
     c.free_blocks.clear();
@@ -80,23 +85,48 @@ void trim_locked(DeviceCache &c) {
 }
 }  // namespace
 
+int poison_fill(void *p, size_t bytes) {
+    const int byte = g_poison_byte.load(std::memory_order_relaxed);
+    if (byte < 0) return CYTO_OK;
+    // the block is idle (nobody owns it yet); its new owner works on a non-blocking stream, which does not order itself behind the
+    // null stream: the fill is complete before this returns
+    CYTO_HIP(hipMemset(p, byte, bytes));
+    CYTO_HIP(hipStreamSynchronize(nullptr));
+    g_poison_fills.fetch_add(1, std::memory_order_relaxed);
+    g_poison_bytes.fetch_add((long long)bytes, std::memory_order_relaxed);
+    return CYTO_OK;
+}
+
+namespace {
+// a block on its way out of cache_alloc (outside g_cache_mutex): filled when the poison mode is on
+void *hand_out(void *p, size_t block_bytes, int *status) {
+    *status = poison_fill(p, block_bytes);
+    if (*status == CYTO_OK) return p;
+    (void)hipGetLastError();
+    cache_release(p, nullptr);
+    return nullptr;
+}
+}  // namespace
+
 void *cache_alloc(size_t bytes, int *status) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) { *status = CYTO_ERR_HIP; return nullptr; }
     const size_t want = round_size(bytes);
+    void *reused = nullptr;
+    size_t reused_bytes = 0;
     {
         std::lock_guard<std::mutex> lk(g_cache_mutex);
         DeviceCache &c = g_cache[dev];
         auto it = c.free_blocks.lower_bound(want);
         // best fit, but never a block more than 25 % larger than asked for (a 10 GB block must not serve a 1 MB request)
         if (it != c.free_blocks.end() && it->first <= want + want / 4 + 4096) {
-            void *p = it->second;
+            reused = it->second;
+            reused_bytes = it->first;
             c.free_bytes -= it->first;
             c.free_blocks.erase(it);
-            *status = CYTO_OK;
-            return p;
         }
     }
+    if (reused) return hand_out(reused, reused_bytes, status);
     void *p = nullptr;
     hipError_t e = hipMalloc(&p, want);
     if (e == hipErrorOutOfMemory) {                 // give the cached blocks back and try once more
@@ -109,10 +139,8 @@ void *cache_alloc(size_t bytes, int *status) {
         *status = e == hipErrorOutOfMemory ? CYTO_ERR_NOMEM : CYTO_ERR_HIP;
         return nullptr;
     }
-    std::lock_guard<std::mutex> lk(g_cache_mutex);
-    g_cache[dev].live[p] = want;
-    *status = CYTO_OK;
-    return p;
+    { std::lock_guard<std::mutex> lk(g_cache_mutex); g_cache[dev].live[p] = want; }
+    return hand_out(p, want, status);
 }
 
 void cache_release(void *p, hipStream_t used_on) {
@@ -217,6 +245,26 @@ int cyto_trim_device_cache(int device_id) {
     std::lock_guard<std::mutex> lk(cyto::g_cache_mutex);
     auto it = cyto::g_cache.find(device_id);
     if (it != cyto::g_cache.end()) cyto::trim_locked(it->second);
+    return CYTO_OK;
+}
+
+int cyto_cache_poison(int byte) {
+    if (byte < -1 || byte > 255) return CYTO_ERR_BAD_ARG;
+    cyto::g_poison_byte.store(byte, std::memory_order_relaxed);
+    return CYTO_OK;
+}
+
+long long cyto_cache_poison_fills(void) { return cyto::g_poison_fills.load(); }
+long long cyto_cache_poison_bytes(void) { return cyto::g_poison_bytes.load(); }
+
+int cyto_cache_peek(size_t bytes, void *host_out, int device_id) {
+    if (!host_out || bytes == 0) return CYTO_ERR_BAD_ARG;
+    int rc = cyto::select_device(device_id);
+    if (rc) return rc;
+    cyto::DevBuf b;
+    rc = b.alloc(bytes);
+    if (rc) return rc;
+    CYTO_HIP(hipMemcpy(host_out, b.p, bytes, hipMemcpyDeviceToHost));
     return CYTO_OK;
 }
 

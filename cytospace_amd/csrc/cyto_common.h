@@ -26,6 +26,9 @@ void set_hip_error(hipError_t e, const char *what);
 // stream never races with work still in flight.  cyto_trim_device_cache() gives everything back to the runtime.
 void *cache_alloc(size_t bytes, int *status);
 void cache_release(void *p, hipStream_t used_on);
+// The poison hook (cyto_cache_poison, a test's tool): while it is on, fills a block that is about to be handed out with the byte and
+// waits for the fill; off, one relaxed atomic load.  CYTO_OK / a HIP status.
+int poison_fill(void *p, size_t bytes);
 
 // RAII device buffer -- host-side convenience only.
 struct DevBuf {
@@ -63,7 +66,7 @@ struct Mem {
             set_hip_error(e, "hipMalloc (plain buffer)");
             return e == hipErrorOutOfMemory ? CYTO_ERR_NOMEM : CYTO_ERR_HIP;
         }
-        return CYTO_OK;
+        return poison_fill(p, bytes ? bytes : 16);
     }
     template <typename U> U *as() const { return reinterpret_cast<U *>(p); }
 };

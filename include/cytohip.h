@@ -61,6 +61,17 @@ int cyto_device_synchronize(int device_id);
  * stream of chunk solves performs no hipMalloc / hipFree: hipFree would synchronise the whole device and serialise the
  * chunks that run side by side).  This returns every cached block to the runtime. */
 int cyto_trim_device_cache(int device_id);
+/* Test hook: neither the cache nor the plain large buffers initialise what they hand out, so a word a kernel reads before anyone
+ * wrote it reads as zero on a fresh block and as the previous solve's state on a reused one.  cyto_cache_poison(byte) with byte in
+ * 0...255 makes every block the cache hands out (fresh or reused, over its whole rounded size) and every plain large buffer arrive
+ * filled with that byte, the fill complete before the allocation returns; -1 turns the mode off (the default; off costs one relaxed
+ * atomic load per allocation).  Process-wide, needs no device; anything else is CYTO_ERR_BAD_ARG.  cyto_cache_poison_fills() /
+ * cyto_cache_poison_bytes() count the fills and the bytes filled in this process.  cyto_cache_peek takes a block of `bytes` from the
+ * cache, copies its first `bytes` to host_out and releases it (tests/test_work_buffers_gpu.py). */
+int cyto_cache_poison(int byte);
+long long cyto_cache_poison_fills(void);
+long long cyto_cache_poison_bytes(void);
+int cyto_cache_peek(size_t bytes, void *host_out, int device_id);
 
 /* ---- Device inputs and caller streams: what holds for every entry point below that takes a device matrix (cost_on_device,
  * x_on_device, cyto_matrix.on_device) or a `void *stream` (tests/test_device_inputs_gpu.py, tests/test_caller_stream_gpu.py).

@@ -21,8 +21,32 @@ def test_library_exports_every_declared_symbol():
     assert len(names) >= 14
     for nme in names:
         assert hasattr(L, nme), f"{nme} declared in cytohip.h but not exported"
+    # the block cache's test hook (tests/test_work_buffers_gpu.py) is part of the header, so the loop above covers it
+    for nme in ("cyto_trim_device_cache", "cyto_cache_poison", "cyto_cache_poison_fills", "cyto_cache_poison_bytes", "cyto_cache_peek"):
+        assert nme in names and hasattr(L, nme), nme
     assert L.cyto_version().decode().startswith("cytohip")
     assert L.cyto_strerror(2).decode() == "cost matrix contains NaN or Inf"
+
+
+def test_cache_poison_switch_needs_no_device():
+    # cyto_cache_poison: a process-wide switch held in atomics; 0...255 on, -1 off, anything else CYTO_ERR_BAD_ARG; nothing is
+    # filled (and no device is touched) until a block is handed out
+    from cytospace_amd import _lib
+    L = _lib.lib()
+    f0, b0 = _lib.cache_poison_fills(), _lib.cache_poison_bytes()
+    try:
+        for bad in (-2, 256, 1000, -(2**31)):
+            assert L.cyto_cache_poison(bad) == 1
+        for ok in (0, 0x7F, 0x80, 0xFF, -1):
+            assert L.cyto_cache_poison(ok) == 0
+        _lib.cache_poison(0xFF)
+        _lib.cache_poison(None)
+        room = np.zeros(8, np.uint8)
+        assert L.cyto_cache_peek(0, room.ctypes.data, 0) == 1 and L.cyto_cache_peek(8, None, 0) == 1      # before any device call
+    finally:
+        L.cyto_cache_poison(-1)
+    assert (_lib.cache_poison_fills(), _lib.cache_poison_bytes()) == (f0, b0)
+    assert L.cyto_cache_poison_fills.restype is ctypes.c_longlong and L.cyto_cache_poison_bytes.restype is ctypes.c_longlong
 
 
 def test_build_source_list_is_the_csrc_directory():
