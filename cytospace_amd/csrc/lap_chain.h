@@ -1,7 +1,8 @@
-// lap_chain.h -- what the float32 solver and driver (lap_jv.hip) and the float64 solver (lap_f64.hip) share: vector types and the row
-// indirection, the column reduction's first two kernels, the workgroup-wide reductions of the 1024-thread kernels, agent-scope
-// accesses, and the host functions the two files call in each other.  Device code here is templates and inline functions only (a
-// plain __global__ function in a header that two files include would be defined twice).
+// lap_chain.h -- what the float32 driver with its streaming kernels (lap_jv.hip), the float32 chain solver (lap_chain_f32.hip) and the
+// float64 solver (lap_f64.hip) share: vector types and the row indirection, the column reduction's first two kernels, the
+// workgroup-wide reductions of the 1024-thread kernels, agent-scope accesses, and the host functions lap_jv.hip and lap_f64.hip call
+// in each other.  Device code here is templates and inline functions only (a plain __global__ function in a header that several
+// files include would be defined more than once).
 #pragma once
 #include "cyto_common.h"
 #include "lap_dev.h"

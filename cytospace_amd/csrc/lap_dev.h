@@ -1,5 +1,6 @@
-// lap_dev.h -- device helpers shared by the LAP kernels (lap_jv.hip: the float32 chain solver; lap_f64.hip: the float64 solver;
-// lap_wide.hip: the wide solver; lap_exact.hip: the certificate and the exact option):
+// lap_dev.h -- device helpers shared by the LAP kernels (lap_jv.hip: the streaming kernels of every float32 solve; lap_chain_f32.hip:
+// the float32 chain solver; lap_f64.hip: the float64 solver; lap_wide.hip: the wide solver; lap_exact.hip: the certificate and the
+// exact option):
 // the status block of a solve (LapStatus) with its counter and timer indices, order-preserving float keys, DPP wave reductions, the
 // LDS-only barrier, the row-cache constants.
 #pragma once
@@ -60,6 +61,8 @@ constexpr int KC = 64;             // cache slots per row (one per lane of a wav
 constexpr int KCU = 63;            // usable entries; slot 63 = { COLSENT, floor }
 constexpr uint64_t KEYMAX = ~0ull;
 constexpr uint32_t COLSENT = 0xFFFFFFFFu;
+
+typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));      // what a 16-byte raw buffer load returns
 
 __device__ __forceinline__ uint32_t f2ord(float h) {
     const uint32_t b = __float_as_uint(h + 0.0f);  // +0.0f: -0 -> +0 so that equal floats get equal keys

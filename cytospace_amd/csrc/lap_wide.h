@@ -1,6 +1,8 @@
-// lap_wide.h -- the interface between the float32 driver (lap_jv.hip) and the wide solver (lap_wide.hip).
+// lap_wide.h -- the interface between the float32 driver (lap_jv.hip) and the wide solver (lap_wide.hip); the row-cache build and the
+// description of a problem (SolveJob) also serve the float32 chain solver (lap_chain_f32.h).
 #pragma once
 #include "cyto_common.h"
+#include "lap_dev.h"
 #include <vector>
 
 namespace cyto {
@@ -18,8 +20,10 @@ struct CachePlan {
 int build_caches(const CachePlan &cp, int n, int64_t ld, const float *cost, const int32_t *rowmap, const float *v, uint32_t *cache_col,
                  float *cache_val, const int32_t *same, hipStream_t stream, const int32_t *rowlist = nullptr, int count = 0);
 
-// One problem of a batch as the float32 driver has set it up (lap_jv.hip: F32Job, private to it, after the column reduction).  Device memory.
-struct WideJob {
+// One problem of a batch as the float32 driver has set it up (lap_jv.hip: F32Job, private to it, after the column reduction), for
+// either solver.  Device memory.  (The slots of fws / iws are named as the wide solver uses them; the chain solver's use: Chain2Args and
+// LazyArgs, lap_chain_f32.hip.  first_rows / first_count: the wide solver only.)
+struct SolveJob {
     const float *cost; int64_t ld;
     const int32_t *rowmap;              // [n] LAP row i reads stored row rowmap[i], or null
     float *fws;                         // [6n + 16] v | u | - | cassign | label (2n)
@@ -27,8 +31,9 @@ struct WideJob {
     uint32_t *cache_col; float *cache_val;      // [n][64] row caches
     char *misc;                         // the status block (lap_dev.h: LapStatus)
     const int32_t *same;                // [n] 1 = the row equals the row before it (runs of identical rows), or null
+    const int32_t *rowgid;              // [n] the run of identical rows that a row is in, counted from 0 (the chain solver; n >= 2)
     int ngroups;                        // runs of identical rows (n: none)
-    DevBuf *state;                      // the solver's own state: allocated here
+    DevBuf *state;                      // the solver's own state, the caller's buffers: one (wide), CHAIN_STATE_BUFS (chain); allocated by the solver
     // the first caches came out of the column reduction's pass (lap_jv.hip: fused_fixup) but for these rows; -1: they did not, build all
     const int32_t *first_rows = nullptr; int first_count = -1;
 };
@@ -40,7 +45,9 @@ struct WidePlan {
 };
 // The wide solve of a batch after its column reduction: reduction transfer, row reduction, searches -- one launch per phase for the
 // whole batch.  ev_cache_done is recorded behind the first cache build, ev_arr_done behind the row reduction.
-int wide_solve_batch(const WidePlan &pl, const std::vector<WideJob> &jobs, hipStream_t stream, hipEvent_t ev_cache_done,
+int wide_solve_batch(const WidePlan &pl, const std::vector<SolveJob> &jobs, hipStream_t stream, hipEvent_t ev_cache_done,
                      hipEvent_t ev_arr_done);
+// the wide solver's fields of cyto_lap_info (the driver has zeroed it)
+void wide_info(cyto_lap_info *info, const LapStatus &h);
 
 }  // namespace cyto

@@ -42,7 +42,7 @@
 
 namespace cyto {
 
-// One problem of a batch: the kernels' argument block.  Every pointer is device memory; the work arrays are the driver's (WideJob).
+// One problem of a batch: the kernels' argument block.  Every pointer is device memory; the work arrays are the driver's (SolveJob).
 //   v, u, cassign   [n] prices, row duals (written at the end), c[colsol[j]][j] per column
 //   label           [n] 64-bit search labels (ordered distance << 32 | tight-hop count << 20 | predecessor row); all-ones between searches
 //   bid             [n] 64-bit bids of a row-reduction round (ordered price << 32 | row); all-ones between rounds
@@ -1307,7 +1307,7 @@ struct AugShared {
     // (the queue lives in st_row / st_col / st_val: the one-edge loop between two searches and the rounds of a search never overlap, and
     //  the kernel's static LDS has no room for another 640 bytes beside the dynamic region; their count: npk[] >> 16)
 };
-static_assert(WNW * 2 <= 32, "the queue of a round's full-row relaxations: two halves of the 64-entry staging arrays");
+static_assert(WNW * AP <= 32, "the queue of a round's full-row relaxations: two halves of the 64-entry staging arrays");
 
 // ---- SEVERAL SEARCHES AT ONCE (one problem, PAR): the free rows' searches are independent until they are committed, and most of
 // them are shallow (a few dozen settled columns after the scaled row reduction), so G workgroups run the searches of free rows
@@ -2542,7 +2542,7 @@ static int wide_launch_aug(const WideArgs *d_args, int nb, int n, hipStream_t st
 
 static std::atomic<int> g_par_busy[64];     // per device: a several-searches-at-once kernel (wide_aug<..,PAR>) is in flight
 
-int wide_solve_batch(const WidePlan &pl, const std::vector<WideJob> &jobs, hipStream_t stream, hipEvent_t ev_cache_done,
+int wide_solve_batch(const WidePlan &pl, const std::vector<SolveJob> &jobs, hipStream_t stream, hipEvent_t ev_cache_done,
                      hipEvent_t ev_arr_done) {
     const int n = pl.n, nl = (int)jobs.size();
     if (!nl) return CYTO_OK;
@@ -2550,14 +2550,14 @@ int wide_solve_batch(const WidePlan &pl, const std::vector<WideJob> &jobs, hipSt
     auto build_caches_of = [&](const int32_t *flags) -> int {    // flags: per problem, 0 = nothing left to do for it (or null: all)
         for (int k = 0; k < nl; k++) {
             if (flags && flags[k] == 0) continue;
-            const WideJob &j = jobs[(size_t)k];
+            const SolveJob &j = jobs[(size_t)k];
             const int r = build_caches(pl.cache, n, j.ld, j.cost, j.rowmap, j.fws, j.cache_col, j.cache_val, j.same, stream);
             if (r) return r;
         }
         return CYTO_OK;
     };
     if (nl == 1 && jobs[0].first_count >= 0) {                 // the first caches exist but for the listed rows (lap_jv.hip: fused_fixup)
-        const WideJob &j = jobs[0];
+        const SolveJob &j = jobs[0];
         if ((rc = build_caches(pl.cache, n, j.ld, j.cost, j.rowmap, j.fws, j.cache_col, j.cache_val, j.same, stream, j.first_rows, j.first_count)))
             return rc;
     } else if ((rc = build_caches_of(nullptr))) return rc;
@@ -2570,7 +2570,7 @@ int wide_solve_batch(const WidePlan &pl, const std::vector<WideJob> &jobs, hipSt
     const int embed_knob = CYTO_KNOB("CYTO_AUG_EMBED").set ? CYTO_KNOB("CYTO_AUG_EMBED").value : 1;
     std::vector<WideArgs> h_wa((size_t)nl);
     for (int k = 0; k < nl; k++) {
-        const WideJob &j = jobs[(size_t)k];
+        const SolveJob &j = jobs[(size_t)k];
         // Several searches of ONE problem at once (wide_aug<.., PAR>): by default for a single problem without runs of identical rows
         // from 2 048 rows on (runs of identical rows -- a Visium problem's slots: a tenth as many groups as rows -- finish most of their
         // searches as runs of one-edge steps in the one-workgroup kernel; a sub-spot chunk's few doubled spots do not matter).
@@ -2706,6 +2706,21 @@ int wide_solve_batch(const WidePlan &pl, const std::vector<WideJob> &jobs, hipSt
         if (done) break;
     }
     return CYTO_OK;
+}
+
+void wide_info(cyto_lap_info *info, const LapStatus &h) {
+    const long long *wc = h.wide, *tm = h.timers;       // (timers: diagnostics for tools/wide_large.py; 100 MHz ticks)
+    info->wide = 1;
+    info->aug_handover = -1;                            // (the chain solver's: no hand-over)
+    info->wide_rounds = wc[WC_ROUNDS]; info->wide_retired = wc[WC_RETIRED]; info->wide_dense_arr = wc[WC_DENSE_ARR];
+    info->wide_dense_aug = wc[WC_DENSE_AUG]; info->wide_aug_rounds = wc[WC_AUG_ROUNDS]; info->wide_aug_settled = wc[WC_AUG_PROCESSED];
+    info->wide_trivial = wc[WC_TRIVIAL]; info->wide_verify_passes = wc[WC_VERIFY_PASSES]; info->wide_aug_launches = wc[WC_AUG_LAUNCHES];
+    info->wide_list_rounds = tm[WT_LIST_ROUNDS]; info->wide_chain_rounds = tm[WT_CHAIN_ROUNDS];
+    info->wide_ms_list = tm[WT_LIST_TICKS] * 1e-5; info->wide_ms_chain = tm[WT_CHAIN_TICKS] * 1e-5;
+    info->wide_ms_aug_rounds = tm[WT_AUG_ROUNDS_TICKS] * 1e-5; info->wide_ms_aug_verify = tm[WT_AUG_VERIFY_TICKS] * 1e-5;
+    info->wide_ms_aug_finish = tm[WT_AUG_FINISH_TICKS] * 1e-5; info->wide_ms_aug_trivial = tm[WT_AUG_TRIVIAL_TICKS] * 1e-5;
+    info->wide_arr_launches = tm[WT_ARR_LAUNCHES]; info->wide_scaled = tm[WT_SCALED]; info->wide_phases = tm[WT_PHASES];
+    info->wide_par_batches = tm[WT_PAR_BATCHES]; info->wide_par_discarded = tm[WT_PAR_DISCARDED];
 }
 
 }  // namespace cyto

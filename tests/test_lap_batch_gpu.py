@@ -1,6 +1,6 @@
 """Batched LAP solves against the CPU oracle, bit for bit: same-size groups, sub-batches, slices, failures, device costs.
 
-A batch (cyto_lap_batch_f32_opts -> lap_batch_any -> lap_batch_same_n -> lap_solve_f32_batch -> wide_solve_batch / launch_batch)
+A batch (cyto_lap_batch_f32_opts -> lap_batch_any -> lap_batch_same_n -> lap_solve_f32_batch -> wide_solve_batch / chain_solve_batch)
 is what a CytoSPACE run executes: the chunks of a rank have ONE size, so a production batch is one large same-size group.  The claim
 (cytohip.h): a problem's indices, duals and semantic counters are the oracle's bit for bit, whatever shares its launches.
 Nothing here has a tolerance except `total`, a float64 sum compared within BASELINE.json's 1e-5 * max(1, |total|).
@@ -27,7 +27,7 @@ Group sizes and the constant of the driver each one is there for:
                           take), 127 four of 32 / 32 / 32 / 31 -- the most one launch carries without a developer knob (256 / 8), which
                           is why bid_total / nb never reaches its floor of 64 here
   (c):    11 problems sliced by max_concurrent 1, 2, 3, 4 (`lo += conc` in lap_batch_any_impl runs 11, 6, 4, 3 times), 0 = one slice
-  (d):    6 and 17 problems with rejected ones among them (the WideJob / live list shorter than the job list; 17: inside a sub-batch)
+  (d):    6 and 17 problems with rejected ones among them (the SolveJob list shorter than the job list; 17: inside a sub-batch)
 
 Oracle time, measured on the finished pool in one process with 8 cores: 60 s for the 597 oracle solves of (a)-(e), (g), (h) --
 (a) 38 s, of which the group at n = 4200 takes 30 s; (b) 12 s; (g) 9 s; the rest 2 s.  (f)'s 40 chunk oracles work on cost rows that
