@@ -137,6 +137,13 @@ int lap_batch_any(int nb, const int *n, const float *const *cost, const int64_t 
                   float *const *v, double *total, cyto_lap_info *info, int *status_out, int max_concurrent, int device_id,
                   const cyto_lap_opts *opts) {
     int rc;
+    // cyto_lap_opts.polish belongs to the single-problem entry points (lap_jv.hip: lap_solve_f32_one runs it behind the solve): a batch
+    // has none, and would hand back unpolished results with polished == 0 -- refused for the call, before any solve.  (The exact
+    // option's way out over its edge cap, exact_status 3, calls lap_polish_f64 itself and does not pass through here.)
+    if (opts && opts->polish != 0) {
+        if (status_out) for (int b = 0; b < nb; b++) status_out[b] = CYTO_ERR_BAD_ARG;
+        return CYTO_ERR_BAD_ARG;
+    }
     try {
         return lap_batch_any_impl(nb, n, cost, ld, cost_on_device, rowmap, nu, rowsol, colsol, u, v, total, info, status_out, max_concurrent,
                                   device_id, opts);

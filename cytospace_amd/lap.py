@@ -163,7 +163,8 @@ def _batch_results(st, status, outs, totals, infos, return_info, return_status):
 def lap_solve_batch(costs, device_id=0, max_concurrent=0, return_info=False, opts=None, return_status=False):
     """Solve several independent square LAPs concurrently on one GPU (C ABI: cyto_lap_batch_f32[_opts]).
 
-    costs: list of 2-D float arrays (host).  opts: None or a dict of cyto_lap_opts fields for the whole batch.
+    costs: list of 2-D float arrays (host).  opts: None or a dict of cyto_lap_opts fields for the whole batch (polish is a
+    single-problem option: a batch refuses it with ValueError before anything is solved).
     Returns a list of dicts like lap_solve().  return_status=True: (that list, [status per problem]) -- a problem with
     non-finite costs is None in the list and CYTO_ERR_NONFINITE in the statuses instead of an exception for the call."""
     L = _lib.lib()

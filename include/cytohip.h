@@ -232,7 +232,10 @@ typedef struct {
                                    finish in float64 -- the matrix widened on the device (n^2 x 8 more bytes), the float32 prices as the start with
                                    every row free, the float64 augmenting row reduction and augmentation of the force_doubles path (~1.2 n steps):
                                    the optimum of the float32 matrix in float64 arithmetic, indices that do not depend on the float32 solver's
-                                   constants.  Several times the cost of the solve: off by default.  (the second of the reserved words) */
+                                   constants.  Several times the cost of the solve: off by default.  Single problems only (cyto_lap_f32_opts,
+                                   cyto_lap_f32_rowmap): a batch has no polish, and cyto_lap_batch_f32_opts with polish != 0 returns
+                                   CYTO_ERR_BAD_ARG for the call (every status_out entry too) before anything is solved.
+                                   cyto_ctx_assign_chunks takes no options and never polishes.  (the second of the reserved words) */
     int32_t exact;              /* float32: the optimum of the float32 matrix (computed in float64), as lapjv returns it -- for single problems,
                                    row maps and batches alike.  Implies certify.  With pi = the float32 result, v its prices, and in float64
                                    w_ij = c_ij - v_j, r_ij = w_ij - w_i,pi(i) and gap = cyto_lap_info.gap_f64, every assignment at least as
@@ -294,7 +297,8 @@ int cyto_lap_batch_f32(int nb, const int *n, const float *const *cost, const int
 int cyto_lap_batch_f32_opts(int nb, const int *n, const float *const *cost, const int64_t *ld, int cost_on_device,
                             int32_t *const *rowsol, int32_t *const *colsol, float *const *u, float *const *v,
                             double *total, cyto_lap_info *info, int *status_out, int max_concurrent, int device_id,
-                            const cyto_lap_opts *opts);     /* opts->mode selects the solver for the whole batch (NULL: defaults) */
+                            const cyto_lap_opts *opts);     /* opts->mode selects the solver for the whole batch (NULL: defaults);
+                                                               opts->polish != 0: CYTO_ERR_BAD_ARG, nothing is solved */
 
 /* ---- A8 (several GPUs, one process each): the only collective on the path is the broadcast of the
  * shared standardised ST matrix (RCCL over xGMI).  id128: 128-byte ncclUniqueId made on one rank by

@@ -28,6 +28,7 @@ Group sizes and the constant of the driver each one is there for:
                           is why bid_total / nb never reaches its floor of 64 here
   (c):    11 problems sliced by max_concurrent 1, 2, 3, 4 (`lo += conc` in lap_batch_any_impl runs 11, 6, 4, 3 times), 0 = one slice
   (d):    6 and 17 problems with rejected ones among them (the SolveJob list shorter than the job list; 17: inside a sub-batch)
+  (i):    cyto_lap_opts.polish, which a batch does not have: refused for the call, and the next batch is the oracle's
 
 Oracle time, measured on the finished pool in one process with 8 cores: 60 s for the 597 oracle solves of (a)-(e), (g), (h) --
 (a) 38 s, of which the group at n = 4200 takes 30 s; (b) 12 s; (g) 9 s; the rest 2 s.  (f)'s 40 chunk oracles work on cost rows that
@@ -441,3 +442,20 @@ def test_h_the_largest_group_twice_and_from_two_threads(chain):
         for q, (nm, g) in enumerate(zip(halves[t], out[t])):
             _equals_oracle(g, nm, chain, tag=f"thread {t} problem {q}")
     assert _bits(out[0]) == a[:17] and _bits(out[1]) == a[16:]
+
+
+# ---- (i) an option a batch does not have ----
+
+def test_i_polish_is_refused_on_a_batch():
+    # cyto_lap_opts.polish is the single-problem calls' (lap_solve_f32_one runs it behind the solve): a batch used to accept it and
+    # return unpolished results with polished == 0.  Now CYTO_ERR_BAD_ARG for the call -- every problem's status too, nothing solved
+    # -- and the next plain batch is the oracle's
+    names = [_name(k, 300) for k in (1, 2, 3, 5)]
+    costs = [_cost(nm) for nm in names]
+    for opts in (dict(polish=1), dict(polish=1, mode=1), dict(polish=1, certify=1)):
+        with pytest.raises(ValueError):
+            lap_solve_batch(costs, return_info=True, opts=opts)
+        with pytest.raises(ValueError):
+            lap_solve_batch(costs, return_info=True, opts=opts, return_status=True)     # not a per-problem rejection: it raises as well
+    _solve_and_check(names, None, False, tag="after the refused call")
+    _solve_and_check(names, CHAIN, True, tag="after the refused call")

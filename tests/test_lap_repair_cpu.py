@@ -140,3 +140,15 @@ def test_exact_option_argument_errors_need_no_device():
         lapjv_hip(c, force_doubles=True, exact=True)
     assert _lib.LapInfo().exact_status == 0
 
+
+def test_polish_on_a_batch_is_refused_without_a_device():
+    # cyto_lap_opts.polish belongs to the single-problem calls: cyto_lap_batch_f32_opts refuses it for the whole call, every
+    # problem's status included, before a device is selected (a batch used to return unpolished results with polished == 0)
+    from cytospace_amd.lap import lap_solve_batch
+    costs = [np.random.default_rng(s).random((16, 16)).astype(np.float32) for s in (1, 2, 3)]
+    for opts in (dict(polish=1), dict(polish=1, certify=1), dict(polish=1, mode=1)):
+        with pytest.raises(ValueError, match="status 1:"):
+            lap_solve_batch(costs, opts=opts)
+        with pytest.raises(ValueError, match="status 1:"):
+            lap_solve_batch(costs, opts=opts, return_status=True)
+

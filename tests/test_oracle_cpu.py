@@ -337,3 +337,33 @@ def test_wide_large_goldens_are_certified(tag):
     assert abs(float(d["total"]) - float(c["total"])) <= 1e-5 * max(1.0, abs(float(c["total"])))
     st = dict(zip([str(k) for k in d["stats_keys"]], d["stats_vals"].tolist()))
     assert st["arr_scaled"] == (0 if tag.startswith("c3s") else 1)     # made with the eps-scaled restatement (round 4)
+
+
+# ---- the float64 restatements on the classes of test_lap_f64_classes_gpu.py: a wrong restatement must not pass by agreeing with a
+# wrong kernel ----
+
+def _f64_class_cases():
+    from _f64_classes import CLASSES
+    return [(cls, n) for cls in CLASSES for n in (65, 300)]
+
+
+@pytest.mark.parametrize("warm", [False, True], ids=["cold", "warm"])
+@pytest.mark.parametrize("cls,n", _f64_class_cases())
+def test_float64_oracles_on_the_instance_classes_vs_scipy(cls, n, warm):
+    from _f64_classes import UNIQUE, make, scipy_solve, spots
+    c = make(cls, n)
+    o = jv_oracle(c, np.float64, warm=warm)
+    sc_cols, opt = scipy_solve(cls, n, c)
+    ar = np.arange(n)
+    assert np.array_equal(np.sort(o["colsol"]), ar) and np.array_equal(o["rowsol"][o["colsol"]], ar)
+    mine = float(c[ar, o["rowsol"]].sum())
+    assert abs(mine - opt) <= 1e-9 * max(1.0, abs(opt)) and abs(o["total"] - opt) <= 1e-9 * max(1.0, abs(opt))
+    if cls in UNIQUE:
+        assert np.array_equal(o["rowsol"], sc_cols)                    # a generic unique optimum: scipy's indices
+    loc = spots(cls, n)
+    if loc is not None:
+        assert np.array_equal(loc[o["colsol"]], loc[np.argsort(sc_cols)])     # repeated rows: scipy's spot for every column
+    if cls.startswith("sub32"):
+        assert len(np.unique(c.astype(np.float32))) <= 4               # what the class is for: the narrowed copy is degenerate
+    if cls == "types":
+        assert o["stats"].arr_budget_hit == (0 if warm else 1)         # the cold chain is cut at the row reduction's step budget
