@@ -84,6 +84,12 @@ class MtxInfo(ctypes.Structure):
                 ("ms_download", ctypes.c_double), ("ms_write", ctypes.c_double)]
 
 
+class MtxReadInfo(ctypes.Structure):
+    """cyto_mtx_read_info (include/cytohip.h)."""
+    _fields_ = [(k, ctypes.c_int64) for k in ("entries", "duplicates", "reason_kind", "reason_line", "reason_byte")] + \
+        [(k, ctypes.c_double) for k in ("ms_read", "ms_upload", "ms_kernels", "ms_download")]
+
+
 class Chunk(ctypes.Structure):
     """cyto_chunk (include/cytohip.h)."""
     _fields_ = [("idx_sc", ctypes.c_void_p), ("n_sc", ctypes.c_int32), ("idx_st", ctypes.c_void_p), ("n_st", ctypes.c_int32),
@@ -196,6 +202,10 @@ def lib():
         L.cyto_mtx_write.restype = ctypes.c_int
         L.cyto_mtx_format_entries.argtypes = [vp, vp, vp, i32, i64, vp, vp]
         L.cyto_mtx_format_entries.restype = ctypes.c_int
+        L.cyto_mtx_read.argtypes = [ctypes.c_char_p, i64, i64, i64, i64, i32, vp, i64, i32, ctypes.POINTER(MtxReadInfo)]
+        L.cyto_mtx_read.restype = ctypes.c_int
+        L.cyto_mtx_parse_entries.argtypes = [vp, i64, vp, i32, i64, i64, vp, vp, vp, vp, vp]
+        L.cyto_mtx_parse_entries.restype = ctypes.c_int
         L.cyto_comm_unique_id.argtypes = [ctypes.c_char_p]
         L.cyto_comm_init.argtypes = [ctypes.c_char_p, i32, i32, i32, ctypes.POINTER(vp)]
         L.cyto_comm_init_local.argtypes = [i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(vp)]

@@ -77,18 +77,7 @@ def read_file(file_path, keep_sparse=True):
         import scipy.io
         if not os.path.isfile(file_path):
             raise IOError("Cannot locate file: {}".format(file_path))
-        base = os.path.dirname(file_path) + os.path.sep
-
-        def find(names):
-            for name in names:
-                for ext in (".tsv", ".csv", ".tsv.gz", ".csv.gz"):
-                    if os.path.isfile(f"{base}{name}{ext}"):
-                        return f"{base}{name}{ext}", ext
-            raise IOError(f"Required files not found for base path: {base}")
-        gpath, gext = find(["genes", "features"])
-        cpath, cext = find(["cells", "barcodes"])
-        genes = pd.read_csv(gpath, sep="\t" if ".tsv" in gext else ",", header=None).iloc[:, 0].to_numpy()
-        cells = pd.read_csv(cpath, sep="\t" if ".tsv" in cext else ",", header=None).iloc[:, 0].to_numpy()
+        genes, cells, gpath, cpath = _mtx_labels(file_path)
         m = scipy.io.mmread(file_path)
         if m.shape != (len(genes), len(cells)):
             raise IOError("The dimensions of the provided sparse matrix does not match the corresponding gene and cell lists. "
@@ -97,6 +86,26 @@ def read_file(file_path, keep_sparse=True):
         return df if keep_sparse else df.sparse.to_dense()
     sep = "," if file_path.lower().endswith(".csv") else "\t"
     return pd.read_csv(file_path, sep=sep, header=0, index_col=0)
+
+
+def _mtx_labels(file_path):
+    """The gene and cell lists beside a MatrixMarket file (genes|features and cells|barcodes, .tsv / .csv, plain or .gz), as
+    cytospace/common/common.py:27-52 reads them: (genes, cells, genes' path, cells' path).  IOError if one is missing."""
+    import os
+    import pandas as pd
+    base = os.path.dirname(file_path) + os.path.sep
+
+    def find(names):
+        for name in names:
+            for ext in (".tsv", ".csv", ".tsv.gz", ".csv.gz"):
+                if os.path.isfile(f"{base}{name}{ext}"):
+                    return f"{base}{name}{ext}", ext
+        raise IOError(f"Required files not found for base path: {base}")
+    gpath, gext = find(["genes", "features"])
+    cpath, cext = find(["cells", "barcodes"])
+    genes = pd.read_csv(gpath, sep="\t" if ".tsv" in gext else ",", header=None).iloc[:, 0].to_numpy()
+    cells = pd.read_csv(cpath, sep="\t" if ".tsv" in cext else ",", header=None).iloc[:, 0].to_numpy()
+    return genes, cells, gpath, cpath
 
 
 # why cyto_table_read refused a file (CYTO_TABLE_ERR_*): read_file_device's info["reason"]["kind"]
@@ -251,6 +260,156 @@ def parse_table_tokens(tokens):
     buf = ctypes.create_string_buffer(text, len(text) + 1)
     _lib.check(_lib.lib().cyto_table_parse_tokens(buf, n, off.ctypes.data, value.ctypes.data, ints.ctypes.data, kind.ctypes.data))
     return kind, value, ints
+
+
+# why cyto_mtx_read refused a body (CYTO_MTXR_ERR_*): read_mtx_device's info["reason"]["kind"]
+_MTX_REFUSALS = {1: "io", 2: "byte", 3: "carriage return", 4: "entry count", 5: "blank line", 6: "fields", 7: "index", 8: "token",
+                 9: "inexact", 10: "negative zero", 11: "duplicate entry", 12: "memory"}
+_MTX_HEAD_BYTES = 1 << 20
+# scipy's reader wants the banner's first word as it is spelt; the other words in any case
+_MTX_BANNER = rb"%%MatrixMarket(?i:[ \t]+matrix[ \t]+coordinate[ \t]+(integer|real)[ \t]+general)[ \t]*\r?\n"
+_MTX_SIZE = rb"[ \t]*(\d{1,18})[ \t]+(\d{1,18})[ \t]+(\d{1,18})[ \t]*(\r?\n)?"
+
+
+def parse_mtx_header(head, file_size):
+    """The header of a MatrixMarket file inside the device grammar, from the file's first bytes `head` (at most
+    the first MiB is looked at): the banner `%%MatrixMarket matrix coordinate integer|real general`, lines starting with '%', then
+    the size line of three [0-9]{1,18} tokens.  Returns {"field": 0 integer / 1 real, "G", "C", "nnz", "data_offset", "lines"} --
+    or the 1-based line at which the header leaves the grammar (another format or symmetry, a blank line, G or C of 0, a size line
+    that is not three such tokens, no size line within the first MiB)."""
+    import re
+    head = bytes(head[:_MTX_HEAD_BYTES])
+    end = head.find(b"\n") + 1
+    m = re.fullmatch(_MTX_BANNER, head[:end]) if end else None
+    if m is None:
+        return 1
+    field = 0 if m.group(1).lower() == b"integer" else 1
+    line = 1
+    while True:
+        line += 1
+        start, end = end, head.find(b"\n", end) + 1
+        if not end:                                       # no line end: the size line of a file that stops there, or nothing
+            end = len(head)
+            if end != file_size or end == start:
+                return line
+        if head[start:start + 1] == b"%":
+            if head[end - 1:end] != b"\n":
+                return line
+            continue
+        m = re.fullmatch(_MTX_SIZE, head[start:end])
+        if m is None:
+            return line
+        G, C, nnz = (int(m.group(k)) for k in (1, 2, 3))
+        if G == 0 or C == 0:
+            return line
+        return {"field": field, "G": G, "C": C, "nnz": nnz, "data_offset": end, "lines": line}
+
+
+def _mtx_frame(genes, cells, words, field):
+    """read_mtx_device's DataFrame from the label lists and the G x C result words (int64 values, or float64 bits for field 1)."""
+    import pandas as pd
+    return pd.DataFrame(words if field == 0 else words.view(np.float64), index=genes, columns=cells, copy=False)
+
+
+def _mtx_on_device(file_path, device_id, info):
+    """read_mtx_device's device path: the DataFrame, or None (info["reason"] says why) for a file outside its grammar."""
+    import os
+    import time
+    import pandas as pd
+
+    def refuse(kind, line=0, byte=0):
+        info["reason"] = {"kind": kind, "line": int(line), "byte": int(byte)}
+        return None
+    if not isinstance(file_path, str):
+        return refuse("not a path")
+    if file_path.endswith(".mtx.gz"):
+        return refuse("compressed")
+    if not file_path.endswith(".mtx"):
+        return refuse("not matrix market")
+    if not os.path.isfile(file_path):
+        return refuse("io")
+    t = time.perf_counter()
+    try:
+        genes, cells, _, _ = _mtx_labels(file_path)
+        # (DataFrame.sparse.to_dense goes through a dict keyed by column label: with a repeated or missing label it is not the matrix)
+        if pd.Index(cells).has_duplicates or pd.isna(cells).any():
+            return refuse("labels")
+    except Exception:
+        return refuse("labels")
+    info["labels_s"] = time.perf_counter() - t
+    t = time.perf_counter()
+    try:
+        with open(file_path, "rb") as f:
+            head = f.read(_MTX_HEAD_BYTES)
+            size = os.fstat(f.fileno()).st_size
+    except OSError:
+        return refuse("io")
+    h = parse_mtx_header(head, size)
+    info["header_s"] = time.perf_counter() - t
+    if not isinstance(h, dict):
+        return refuse("header", h)
+    if (h["G"], h["C"]) != (len(genes), len(cells)):
+        return refuse("shape", h["lines"])
+    try:
+        words = np.empty((h["G"], h["C"]), np.int64)
+    except MemoryError:
+        return refuse("memory")
+    r = _lib.MtxReadInfo()
+    st = _lib.lib().cyto_mtx_read(file_path.encode(), h["data_offset"], h["G"], h["C"], h["nnz"], h["field"], words.ctypes.data,
+                                  h["C"], device_id, ctypes.byref(r))
+    info.update(file_read_s=r.ms_read / 1e3, upload_s=r.ms_upload / 1e3, kernels_s=r.ms_kernels / 1e3, download_s=r.ms_download / 1e3)
+    if st == _lib.CYTO_ERR_UNSUPPORTED:
+        return refuse(_MTX_REFUSALS.get(r.reason_kind, str(r.reason_kind)), r.reason_line, r.reason_byte)
+    if st == 3:                                                              # CYTO_ERR_NOMEM
+        return refuse("memory")
+    _lib.check(st)
+    info.update(field="integer" if h["field"] == 0 else "real", entries=int(r.entries), duplicates=int(r.duplicates))
+    t = time.perf_counter()
+    df = _mtx_frame(genes, cells, words, h["field"])
+    info["dataframe_s"] = time.perf_counter() - t
+    return df
+
+
+def read_mtx_device(file_path, device_id=0, return_info=False):
+    """read_file(file_path, keep_sparse=False) for a MatrixMarket `.mtx` file with its genes|features and cells|barcodes lists
+    beside it, the body parsed and made dense on the GPU (C ABI: cyto_mtx_read; csrc/mtx_read.hip).  The result is equal to
+    read_file's: the index from the gene list, the columns from the cell list (both read by the pd.read_csv calls of read_file),
+    every column int64 for an `integer` file and float64 for a `real` one, every value bit for bit, duplicate entries of an
+    integer file summed.  A file outside the grammar of DESIGN.md 4.1e -- `.mtx.gz`, another banner than `coordinate integer|real
+    general`, a body with empty lines, comments, a `+`, values scipy's converter would have to round twice, negative zeros,
+    duplicate entries in a real file, repeated cell labels -- and every file read_file raises for (missing, without its lists, a
+    size line that disagrees with them, a malformed body) is read by read_file itself: its result, or its exception.
+
+    return_info: also return a dict -- "path" ("device" or "scipy"), for a fallback "reason" {"kind", "line", "byte"}, for the
+    device path "field" ("integer" / "real"), "entries" and "duplicates" (entries that met a non-zero sum in their cell), and the
+    phase times in seconds: labels_s (the two lists), header_s, file_read_s, upload_s (what the upload added to the reads),
+    kernels_s (zero fill included), download_s, dataframe_s, total_s."""
+    import time
+    t = time.perf_counter()
+    info = {"path": "device"}
+    df = _mtx_on_device(file_path, device_id, info)
+    if df is None:
+        info["path"] = "scipy"
+        df = read_file(file_path, keep_sparse=False)
+    info["total_s"] = time.perf_counter() - t
+    return (df, info) if return_info else df
+
+
+def parse_mtx_entries(lines, field, G, C):
+    """The device reader's entry-line parser, run on the host (C ABI: cyto_mtx_parse_entries, a test hook).  lines: a list of
+    bytes, each an entry line without its line end; field 0 integer / 1 real.  Returns (kind, where, row, col, value): kind 0 or
+    the CYTO_MTXR_ERR_* code, where the offset in the line that the refusal names, row and col 1-based, value the int64 value or
+    the float64 bits."""
+    text = b"".join(lines)
+    n = len(lines)
+    off = np.zeros(n + 1, np.int64)
+    np.cumsum([len(r) for r in lines], out=off[1:])
+    kind = np.empty(n, np.int8)
+    where, row, col, value = (np.empty(n, np.int64) for _ in range(4))
+    buf = ctypes.create_string_buffer(text, len(text) + 1)
+    _lib.check(_lib.lib().cyto_mtx_parse_entries(buf, n, off.ctypes.data, field, G, C, kind.ctypes.data, where.ctypes.data,
+                                                 row.ctypes.data, col.ctypes.data, value.ctypes.data))
+    return kind, where, row, col, value
 
 
 def downsample(data_df, target_count):

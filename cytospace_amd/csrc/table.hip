@@ -11,7 +11,7 @@
 //                Pass 1 checks the field count and every token and sets the per-column "has a decimal token" flags; pass 2
 //                writes every value in its column's final type (int64 or float64 bits) into the G x C row-major result.
 //   tbl_labels   packs the row labels (field 0), one per line, for pandas to infer the index from.
-#include "cyto_common.h"
+#include "text_scan.h"
 
 #include <fcntl.h>
 #include <math.h>
@@ -134,43 +134,7 @@ __host__ __device__ inline int parse_token(const uint8_t *p, const uint8_t *e, d
     return integer ? TOK_INT : TOK_DEC;
 }
 
-__device__ __forceinline__ void note_error(unsigned long long *err, int64_t pos, int kind) {
-    atomicMin(err, ((unsigned long long)pos << 8) | (unsigned long long)kind);
-}
-
-constexpr int WG = 256;
-
-// Exclusive scan of one value per thread across the 256-thread workgroup; *total: the sum.  Every thread must call it.
-__device__ __forceinline__ int wg_scan(int v, int *total) {
-    __shared__ int wsum[WG / 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int y = __shfl_up(x, off, 64);
-        if (lane >= off) x += y;
-    }
-    if (lane == 63) wsum[w] = x;
-    __syncthreads();
-    int before = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < WG / 64; i++) {
-        before += i < w ? wsum[i] : 0;
-        tot += wsum[i];
-    }
-    __syncthreads();                                    // (wsum is reused by the next call)
-    *total = tot;
-    return before + x - v;
-}
-
-// A thread owns 16 consecutive 16-byte slices (256 bytes), a workgroup 64 KiB.
-constexpr int NL_SLICES = 16;
-constexpr int64_t NL_BLOCK = (int64_t)WG * NL_SLICES * 16;
-
-__device__ __forceinline__ uint8_t byte_of(const uint4 &v, int k) {
-    const uint32_t w = k < 4 ? v.x : k < 8 ? v.y : k < 12 ? v.z : v.w;
-    return (uint8_t)(w >> ((k & 3) * 8));
-}
+// (text_scan.h: note_error, wg_scan, the 64 KiB blocks of the line pass -- a thread owns 16 consecutive 16-byte slices --, byte_of)
 
 // WRITE = false: blk_cnt[b] := '\n' count of block b within [d0, N), and the first byte outside the grammar.
 // WRITE = true: ends[blk_off[b] + rank] := the position of every '\n' of block b.
@@ -221,20 +185,6 @@ __global__ __launch_bounds__(WG) void tbl_lines(const uint8_t *T, int64_t d0, in
             }
         }
     }
-}
-
-// One workgroup: off[b] := exclusive prefix sum of cnt over the nblk blocks, *total := the sum.
-__global__ __launch_bounds__(WG) void tbl_scan_blocks(const int *cnt, int64_t nblk, int64_t *off, int64_t *total) {
-    int64_t carry = 0;
-    for (int64_t b0 = 0; b0 < nblk; b0 += WG) {
-        const int64_t b = b0 + threadIdx.x;
-        const int v = b < nblk ? cnt[b] : 0;
-        int tot;
-        const int ex = wg_scan(v, &tot);
-        if (b < nblk) off[b] = carry + ex;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) *total = carry;
 }
 
 // Data line g: [*s, *e) without its '\n' and a '\r' before it.
@@ -314,17 +264,7 @@ __global__ __launch_bounds__(WG) void tbl_labels(const uint8_t *T, const int64_t
 }
 
 // (Mem, cyto_common.h: the text and the result are as large as the input and do not go through the block cache; Pinned: the two
-// chunk buffers of the streamed upload)
-constexpr size_t CHUNK = size_t(16) << 20;
-
-struct Fd {
-    int fd = -1;
-    ~Fd() { if (fd >= 0) close(fd); }
-};
-
-double ms_since(std::chrono::steady_clock::time_point t) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
-}
+// chunk buffers of the streamed upload; text_scan.h: CHUNK, Fd, ms_since)
 
 // The line of the file (1-based, the header being line 1) that holds byte `pos`; ends: the data lines' ends.
 int64_t file_line(const std::vector<int64_t> &ends, int64_t pos) {

@@ -664,11 +664,12 @@ def read_data(scRNA_path, cell_type_path, cell_type_fraction_estimation_path, n_
               device_id=0):
     """cytospace.py:20-113.  Reads the inputs and prefixes their ids (spots 'SPOT_', cells 'CELL_', genes 'GENE_', cell
     types 'TYPE_'), drops genes listed more than once, orders ST and scRNA columns like the coordinates and cell-type
-    tables, and validates.  The two expression tables (scRNA_path, st_path), when they are delimited text, are parsed on GPU
-    device_id by common.read_file_device (the same DataFrames as read_file; a file outside its grammar is read by read_file);
-    the small tables are read by read_file.  A MatrixMarket input is read dense, as the reference reads it.  Unlike the
+    tables, and validates.  The two expression inputs (scRNA_path, st_path) are parsed on GPU device_id: delimited text by
+    common.read_file_device, a MatrixMarket `.mtx` with its gene and cell lists by common.read_mtx_device (the same DataFrames
+    as read_file, a MatrixMarket input dense as the reference reads it; a file outside their grammars is read by read_file);
+    the small tables are read by read_file.  Unlike the
     reference this never reads a Space Ranger archive or estimates fractions with R: both raise ValueError (see check_supported)."""
-    from .common import read_file, read_file_device
+    from .common import read_file, read_file_device, read_mtx_device
     check_supported(spaceranger_path=spaceranger_path, st_cell_type_path=st_cell_type_path,
                     cell_type_fraction_estimation_path=cell_type_fraction_estimation_path)
     if (st_path is None) and (coordinates_path is None):
@@ -677,14 +678,19 @@ def read_data(scRNA_path, cell_type_path, cell_type_fraction_estimation_path, n_
     def read(path):
         return read_file(path, keep_sparse=False)
 
-    st_data = read_file_device(st_path, device_id)
+    def read_expression(path):
+        if isinstance(path, str) and path.endswith(".mtx"):
+            return read_mtx_device(path, device_id)
+        return read_file_device(path, device_id)
+
+    st_data = read_expression(st_path)
     coordinates_data = read(coordinates_path)
     st_data = st_data[~st_data.index.duplicated(keep=False)]
     st_data.columns = ["SPOT_" + str(c) for c in st_data.columns]
     st_data.index = ["GENE_" + str(g) for g in st_data.index]
     coordinates_data.index = ["SPOT_" + str(s) for s in coordinates_data.index]
 
-    scRNA_data = read_file_device(scRNA_path, device_id)
+    scRNA_data = read_expression(scRNA_path)
     scRNA_data.columns = ["CELL_" + str(c) for c in scRNA_data.columns]
     scRNA_data.index = ["GENE_" + str(g) for g in scRNA_data.index]
     scRNA_data = scRNA_data[~scRNA_data.index.duplicated(keep=False)]

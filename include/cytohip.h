@@ -551,6 +551,50 @@ int cyto_mtx_write(const char *path, int64_t G, int64_t N, const void *x, int64_
 int cyto_mtx_format_entries(const int64_t *rows, const int64_t *cols, const void *values, int dtype, int64_t n, char *out,
                             int64_t *offsets);
 
+/* ---- a MatrixMarket coordinate file read dense (cytospace_amd.common.read_mtx_device): what scipy.io.mmread(path).toarray() holds,
+ * parsed and scattered on the device.  The caller parses the banner, the comments and the size line "G C nnz"; the
+ * nnz entry lines "row col value" start at byte data_offset.  field: 0 integer (out: int64 values, duplicate entries summed with
+ * int64 wrap-around), 1 real (out: float64 bits).  out: G x ldo host words, of which the call writes the first C of every row.
+ * CYTO_ERR_BAD_ARG, before any device is touched: a null pointer, G <= 0, C <= 0, nnz < 0, data_offset < 0, ldo < C, another field.
+ * CYTO_ERR_UNSUPPORTED: the body is outside the grammar and `out` is undefined; info->reason_kind = CYTO_MTXR_ERR_*, reason_line
+ * the file's line (1-based; 0 if none), reason_byte the byte offset.  Which refusal a file with several gets: (1) IO, MEMORY;
+ * (2) the lowest byte at or after data_offset that is outside the allowed set (BYTE) or a '\r' not followed by '\n' (CR);
+ * (3) a line count other than nnz: {COUNT, 0, the lines found}; (4) the lowest (byte, kind) among an empty line (BLANK) and a line
+ * without exactly three tokens (FIELDS), both at the line's first byte, an index outside [0-9]{1,18} or its range (INDEX) and a
+ * value outside its grammar (TOKEN, INEXACT, NEGZERO), at the token's first byte; (5) real field: the second entry, in file order,
+ * of the first cell to hold two non-zero entries (DUPLICATE, at the line's first byte). */
+enum {
+    CYTO_MTXR_ERR_IO = 1,         /* not a readable regular file, shorter than data_offset, or it shrank while read */
+    CYTO_MTXR_ERR_BYTE = 2,       /* a byte other than digits - . e E + space tab '\r' '\n', or a blank as the file's last byte */
+    CYTO_MTXR_ERR_CR = 3,         /* '\r' not followed by '\n' */
+    CYTO_MTXR_ERR_COUNT = 4,      /* the body does not have exactly nnz lines */
+    CYTO_MTXR_ERR_BLANK = 5,      /* an empty line */
+    CYTO_MTXR_ERR_FIELDS = 6,     /* a line without exactly three tokens */
+    CYTO_MTXR_ERR_INDEX = 7,      /* a row or column outside [0-9]{1,18}, below 1 or above G / C */
+    CYTO_MTXR_ERR_TOKEN = 8,      /* a value outside the field's token grammar */
+    CYTO_MTXR_ERR_INEXACT = 9,    /* a real value outside the window in which one IEEE operation gives the correctly rounded value */
+    CYTO_MTXR_ERR_NEGZERO = 10,   /* a real zero with a minus sign */
+    CYTO_MTXR_ERR_DUPLICATE = 11, /* real field: two non-zero entries in one cell (a float sum depends on the order) */
+    CYTO_MTXR_ERR_MEMORY = 12     /* the text and the dense result do not fit in device memory */
+};
+typedef struct cyto_mtx_read_info {
+    int64_t entries;              /* entry lines scattered (nnz) */
+    int64_t duplicates;           /* integer field: entries that found a non-zero sum in their cell (for positive counts: entries
+                                     minus distinct cells) */
+    int64_t reason_kind, reason_line, reason_byte;      /* with CYTO_ERR_UNSUPPORTED, else 0 */
+    double ms_read;               /* host file reads */
+    double ms_upload;             /* what the upload added to them */
+    double ms_kernels;            /* the zero fill, the kernels and the small copies between them */
+    double ms_download;           /* the dense result, device to host */
+} cyto_mtx_read_info;
+int cyto_mtx_read(const char *path, int64_t data_offset, int64_t G, int64_t C, int64_t nnz, int field, int64_t *out, int64_t ldo,
+                  int device_id, cyto_mtx_read_info *info);
+/* The entry-line parser alone, on the host (a test hook): line i is text[offsets[i], offsets[i+1]), without its line end.  kinds[i]
+ * 0 or CYTO_MTXR_ERR_* (BLANK ... NEGZERO), where[i] the offset within the line that a refusal names; rows[i], cols[i] 1-based and
+ * values[i] the int64 value or the float64 bits (kind 0). */
+int cyto_mtx_parse_entries(const char *text, int64_t n, const int64_t *offsets, int field, int64_t G, int64_t C, int8_t *kinds,
+                           int64_t *where, int64_t *rows, int64_t *cols, int64_t *values);
+
 #ifdef __cplusplus
 }
 #endif
