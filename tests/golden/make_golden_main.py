@@ -5,6 +5,8 @@ arguments -- no reference source.  Absent third-party modules are stubbed as in 
 read_file (datatable) is swapped for a pandas reader of the same tables, import_solver for an exact solver with lapjv's return
 shape, and plots are off.  An instance is rejected (and the generator fails) if any of its LAPs gives a different spot-level
 answer when the cost is rounded to float32, so that the float32 GPU solver is expected to reproduce it.
+gv15 (make_golden_main2.py) reuses inputs(), the solver and the stubs from here for the runs these five leave out: the other
+metrics, MatrixMarket and tab-separated inputs, repeated cells, a square result, an output prefix and sizes beyond toys.
 
 Run:  python tests/golden/make_golden_main.py
 """
