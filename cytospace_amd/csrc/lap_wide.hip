@@ -1297,7 +1297,7 @@ struct AugShared {
     int ntouch, any[3], npk[3], fail, anydense, rootdense, doroot, f, err;
     int waste, stop;               // full-row relaxations of this launch; "return to the driver for fresh caches"
     int nhop;                      // edges of the path being flipped
-    int conflict;                  // PAR: this search met a column an earlier search of the batch claimed
+    int nset;                      // PAR: entries of this search's list of settled columns
     int scans;
     int st_row[64], st_col[64];    // one-edge searches: their results, stored to global memory 64 at a time
     float st_val[64];
@@ -1319,10 +1319,10 @@ static_assert(WNW * AP <= 32, "the queue of a round's full-row relaxations: two 
 //   already at or above the search's end; unassigned columns other than the sink keep their prices) -- its labels, sink and path are
 //   the ones it would have computed after the commit.  The first search of a batch that meets an earlier one's set, and every one
 //   after it, is discarded and runs again in the next batch.  Nothing of the restatement changes: same searches, same order, same bits.
-// Conflicts are found without a serial pass: every search claims its columns with an atomic max of (batch << 8 | 255 - g); after a
-// grid barrier a search whose columns all still carry its own key met no smaller g.  The committing workgroups log their price and
-// owner changes; every workgroup applies the log to its LDS copies before the next batch.  Grid barriers: three per batch (the
-// embedded form, wide_aug<.., EMB>: four).
+// Conflicts are found without a serial pass and without a pass of their own: every search claims its columns with a RETURNING atomic max
+// of (batch << 8 | 255 - g), and the word that comes back tells which of two searches of the batch to flag (search_end).  The committing
+// workgroups log their price and owner changes; every workgroup applies the log to its LDS copies before the next batch.  Grid barriers:
+// two per batch -- behind the claims, behind the commits -- and a third in the embedded form, wide_aug<.., EMB>, behind its repair.
 struct ParCtl {
     unsigned int bar_arrive, bar_gen;
     int P[2], nplog[2], nolog[2];          // per batch parity: first conflicting search, entries of the two change logs
@@ -1331,11 +1331,53 @@ struct ParCtl {
 };
 static_assert(sizeof(ParCtl) <= 256, "control block");
 constexpr int PAR_GMAX = 64;
+// -DCYTO_AUG_FIN_SPLIT (a developer build, tools/fin_split.py): the end of every batch by parts, per workgroup -- thread 0's clock at
+// the boundaries, with a workgroup barrier in front of every stamp (so the parts of this build are a little longer than the plain one's)
+#ifdef CYTO_AUG_FIN_SPLIT
+constexpr int FS_MAXB = 2048, FS_G = 16, FS_NP = 14;
+enum { FS_CLAIM, FS_WAIT1, FS_CHECK, FS_WAIT2, FS_UPDATE, FS_WALK, FS_COST, FS_RESET, FS_WAIT3, FS_REPAIR, FS_NTOUCH, FS_SETTLED, FS_HOPS, FS_ARRIVE };
+__device__ long long g_fs[FS_MAXB][FS_G][FS_NP];
+#define FS_OK (PAR && batchno - 1 < FS_MAXB && g < FS_G)
+#define FS_BEGIN() { if (PAR && tid == 0) { fs_mark = wall_clock64(); if (FS_OK) g_fs[batchno - 1][g][FS_ARRIVE] = fs_mark; } }
+#define FS_LAP(part) { if (PAR) { __syncthreads(); if (tid == 0) { const long long fsn_ = wall_clock64(); if (FS_OK) g_fs[batchno - 1][g][part] = fsn_ - fs_mark; fs_mark = fsn_; } } }
+#define FS_SET(part, val) { if (tid == 0 && FS_OK) g_fs[batchno - 1][g][part] = (val); }
+#define FS_COUNT() atomicAdd(&s.st_col[63], 1)
+#else
+#define FS_BEGIN()
+#define FS_LAP(part)
+#define FS_SET(part, val)
+#define FS_COUNT()
+#endif
 static size_t wide_par_state_bytes(int n, int G) {
     const size_t np = ((size_t)n + 63) & ~(size_t)63;
     // control block | labels G x n | touched G x n | hops G x 2n | claim n | price log (col, val) | owner log (col, owner)
-    return 256 + (size_t)G * np * 8 + (size_t)G * np * 4 + (size_t)G * np * 8 + np * 4 + np * 8 + np * 8;
+    // | settled lists (col, distance) G x n | path links by column (pred row, its column) G x n | four links at a time G x 4n
+    return 256 + (size_t)G * np * 8 + (size_t)G * np * 4 + (size_t)G * np * 8 + np * 4 + np * 8 + np * 8 + (size_t)G * np * 8 + (size_t)G * np * 8 +
+           (size_t)G * np * 32;
 }
+// where a search's own arrays are: the problem's (one search at a time) or workgroup g's part of the state above (PAR)
+struct SearchView {
+    unsigned long long *lbl, *setl, *link, *link4;
+    int32_t *tch, *hop_i, *hop_j, *plog_col, *olog_col, *olog_own;
+    uint32_t *claim;
+    float *plog_val;
+    __device__ __forceinline__ SearchView(const WideArgs &a, bool par, int g) {
+        const int G = par ? a.par_groups : 1;
+        const size_t np_ = ((size_t)a.n + 63) & ~(size_t)63;
+        lbl = par ? reinterpret_cast<unsigned long long *>(a.par + 256) + (size_t)g * np_ : a.label;
+        tch = par ? reinterpret_cast<int32_t *>(a.par + 256 + (size_t)G * np_ * 8) + (size_t)g * np_ : a.touched;
+        hop_i = par ? reinterpret_cast<int32_t *>(a.par + 256 + (size_t)G * np_ * 12) + (size_t)g * 2 * np_ : a.act0;
+        hop_j = par ? hop_i + np_ : a.act1;
+        claim = reinterpret_cast<uint32_t *>(a.par + 256 + (size_t)G * np_ * 20);
+        plog_col = reinterpret_cast<int32_t *>(claim + np_);
+        plog_val = reinterpret_cast<float *>(plog_col + np_);
+        olog_col = reinterpret_cast<int32_t *>(plog_val + np_);
+        olog_own = olog_col + np_;
+        setl = reinterpret_cast<unsigned long long *>(olog_own + np_) + (size_t)g * np_;
+        link = reinterpret_cast<unsigned long long *>(olog_own + np_) + ((size_t)G + (size_t)g) * np_;
+        link4 = reinterpret_cast<unsigned long long *>(olog_own + np_) + (2 * (size_t)G + 4 * (size_t)g) * np_;
+    }
+};
 __device__ __forceinline__ void par_barrier(ParCtl *c, int G, unsigned &gen) {
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1440,6 +1482,301 @@ __device__ __noinline__ void embed_repair(gf32_t *cache_red, gci32_t *inv_off, g
     }
 }
 
+// THE END OF A SEARCH (wide_aug): [PAR: claims, the conflict-free prefix of the batch;] price update and path, the new owners, reset.
+// Out of line like embed_repair, and for the same reason: the search rounds must keep the registers they have.  The kernel's LDS arrives
+// as typed pointers (what goes through them stays LDS instructions), the argument block is read again.
+// Returns hops of the flipped path | P of the batch << 32 | (this search was committed) << 48.
+//
+// PAR, the claims: every column a search settled (label below its end's) and its sink get an atomic max of (batch << 8 | 255 - g), which
+// keeps the LOWEST workgroup of the LATEST batch -- and RETURNS the word it replaced.  Within a batch a column's word therefore holds the
+// running lowest g of its claimants: an arrival that is no new running minimum sees a smaller g and flags ITSELF; an arrival that is a new
+// running minimum sees the previous one and flags THAT; so, whatever the order of arrival, every claimant of a column but its lowest is
+// flagged (atomic min into P) -- exactly the searches that found "one of my columns carries another key" in a pass of their own behind a
+// grid barrier before.  Same P, same committed prefix, same batches, same discarded searches.  A word of an earlier batch flags nobody.
+// In the same pass the settled columns go to a list (column, ordered distance), compacted by ballot with one LDS atomic per wave and four
+// steps, and to the path links: by column, (the row that labelled it, that row's column) -- rowsol of a path row is changed by no other
+// search committed in the batch (their settled sets and sinks are disjoint), so the link is what the walk would read.
+// The commit: wave 0 walks the path -- loads only, behind the sink's hop one 8-byte link per hop, or four links per round trip where the
+// search settled 32 columns or more (see there) -- while the other waves update the prices from the list (no label, no touched column
+// that is not settled); behind a barrier all threads store the new owners.
+// The words of a batch's parity (P, log counts): P is written by the claims, between the LAST barrier of the batch before and this
+// batch's first; read behind the first; the log counts grow behind the first and are read behind the second.  Workgroup 0 resets the
+// OTHER parity's words behind the first barrier: their last readers (log counts: behind the second barrier of the batch before) passed
+// it, and their next writers (claims of the next batch) wait behind this batch's second.
+typedef __attribute__((address_space(3))) struct AugShared lds_aug_t;
+typedef __attribute__((address_space(3))) unsigned long long lds_u64_t;
+#ifndef CYTO_WALK_LINKS
+#define CYTO_WALK_LINKS 1          // (0: a developer build whose walk reads label and rowsol per hop, for the comparison)
+#endif
+#ifndef CYTO_WALK_HOP4
+#define CYTO_WALK_HOP4 1           // (0: a developer build that never takes four hops per round trip)
+#endif
+template <bool VLDS, bool CLDS, bool PAR>
+__device__ __noinline__ unsigned long long search_end(const WideArgs *__restrict__ batch, lds_aug_t *sp, lds_u64_t *smem, int g_, int fr_, int batchno_,
+                                                      unsigned pgen_, int active_) {
+    constexpr bool LINKS = PAR && CYTO_WALK_LINKS;
+    AugShared &s = *(AugShared *)sp;
+    const int g = uni(g_), fr = uni(fr_), batchno = uni(batchno_);
+    unsigned pgen = uni(pgen_);
+    const bool active = uni(active_) != 0;
+    const WideArgs a = load_wide_args(batch, PAR ? 0 : blockIdx.x);
+    const int n = a.n, tid = threadIdx.x, lane = tid & 63, w = uni((int)(threadIdx.x >> 6));
+    const int nblk = (n + 63) / 64, nw32 = (n + 31) / 32;
+    const int G = PAR ? a.par_groups : 1;
+    ParCtl *pc = reinterpret_cast<ParCtl *>(a.par);
+    const SearchView sv(a, PAR, g);
+    unsigned long long *lbl = sv.lbl, *setl = sv.setl, *link = sv.link;
+    int32_t *tch = sv.tch, *hop_i = sv.hop_i, *hop_j = sv.hop_j;
+    unsigned long long *bmin = (unsigned long long *)smem;
+    uint32_t *dirty = reinterpret_cast<uint32_t *>(bmin + nblk);
+    uint32_t *asg = dirty + nw32;
+    uint32_t *dense = asg + nw32;
+    float *s_v = reinterpret_cast<float *>(dense + nw32);
+    uint16_t *s_cs = reinterpret_cast<uint16_t *>(s_v + (VLDS ? ((n + 3) & ~3) : 0));
+    auto getv = [&](int j) -> float { return VLDS ? s_v[j] : ld_sc1(a.v + j); };
+    auto is_asg = [&](int c) -> bool { return (asg[c >> 5] >> (c & 31)) & 1u; };
+#ifdef CYTO_AUG_FIN_SPLIT
+    long long fs_mark = 0;
+#endif
+    const unsigned long long Tk = active ? uni((unsigned long long)s.T) : ~0ull;
+    const uint32_t Dord = (uint32_t)(Tk >> 32);
+    const float D = ord2f(Dord);
+    const int sink = (int)lid_of(Tk);
+    const int nt = active ? uni(s.ntouch) : 0;
+    const int par = batchno & 1;
+    bool commit = true;
+    int Pb = G;
+    FS_BEGIN()
+    if (PAR) {
+        const bool have = Tk != ~0ull;
+        if (active && !have && tid == 0) { atomicExch(&pc->err, 1); atomicMin(&pc->P[par], g); }
+        const uint32_t key = ((uint32_t)batchno << 8) | (uint32_t)(255 - g);
+        // (measured, profiles/r09_batch_end_ab.txt: a deep search that shares thousands of columns with a lower one sends as many
+        //  atomic minima to P's address, 110 us for 3 892 columns; a minimum per thread and one atomic per wave is the next step)
+        auto flag = [&](uint32_t old) {                           // old: what a claim's atomic max returned
+            if ((old >> 8) == (uint32_t)batchno && old != key) {
+                const int go = 255 - (int)(old & 255u);
+                atomicMin(&pc->P[par], g > go ? g : go);
+            }
+        };
+        if (have) {
+            // (four touched columns, then their four labels, then the settled ones' rows and claims in flight per thread.  Eight at a
+            //  time was measured: no faster, and the registers it took in here made the search rounds 3 % slower -- the compiler's
+            //  allocation of the kernel follows what this function clobbers)
+            constexpr int CU_ = 4;
+            for (int q0 = 0; q0 < nt; q0 += CU_ * WT) {            // (the same trips in every thread: the ballots below)
+                int k[CU_], pre[CU_], cnt = 0;
+                unsigned long long lb[CU_];
+                uint64_t m[CU_];
+                bool st[CU_];
+#pragma unroll
+                for (int t = 0; t < CU_; t++) { const int q = q0 + t * WT + tid; k[t] = q < nt ? ld_sc1(tch + q) : -1; }
+#pragma unroll
+                for (int t = 0; t < CU_; t++) lb[t] = k[t] >= 0 ? ld_sc1(lbl + k[t]) : ~0ull;
+#pragma unroll
+                for (int t = 0; t < CU_; t++) {
+                    st[t] = k[t] >= 0 && lv_of(lb[t]) < lv_of(Tk) && is_asg(k[t]);
+                    m[t] = __ballot(st[t]); pre[t] = cnt; cnt += __popcll(m[t]);
+                }
+                if (cnt == 0) continue;
+                int rs[CU_];
+#pragma unroll
+                for (int t = 0; t < CU_; t++) rs[t] = LINKS && st[t] ? ld_sc1(a.rowsol + (int)lid_of(lb[t])) : -1;
+                uint32_t old[CU_];
+#pragma unroll
+                for (int t = 0; t < CU_; t++) old[t] = st[t] ? atomicMax(sv.claim + k[t], key) : 0u;
+                int base = 0;
+                if (lane == 0) base = atomicAdd(&s.nset, cnt);
+                base = uni(base);
+#pragma unroll
+                for (int t = 0; t < CU_; t++)
+                    if (st[t]) {
+                        setl[base + pre[t] + __popcll(m[t] & lanemask_lt())] = (lb[t] >> 32 << 32) | (uint32_t)k[t];
+                        if (LINKS) link[k[t]] = ((unsigned long long)(uint32_t)rs[t] << 32) | lid_of(lb[t]);
+                        flag(old[t]);
+                        FS_COUNT();
+                    }
+            }
+            if (tid == 0) flag(atomicMax(sv.claim + sink, key));
+        }
+        FS_LAP(FS_CLAIM)
+        par_barrier(pc, G, pgen);
+        FS_LAP(FS_WAIT1)
+        Pb = uni(ld_sc1(&pc->P[par]));
+        Pb = Pb < G ? Pb : G;
+        if (g == 0 && tid == 0) { st_sc1(&pc->P[par ^ 1], PAR_GMAX + 1); st_sc1(&pc->nplog[par ^ 1], 0); st_sc1(&pc->nolog[par ^ 1], 0); }
+        commit = active && have && g < Pb;
+    }
+    int nhop = 0;
+    if (commit) {
+        // A long path is a chain of dependent round trips (0.4 us each: 340 hops in the deepest search at 50 000^2, 2 074 on the critical
+        // paths of a solve's 34 batches).  Where the search settled more than a few columns, every thread first follows the links of its
+        // settled columns four deep -- the chains of all columns in flight together -- and stores the four links by column; the walk then
+        // takes four hops per round trip.  A link whose row is the free row ends a chain (what follows it repeats it).
+        const int nset = PAR ? uni(s.nset) : 0;
+        // (one column per thread and trip: the chains of four columns per thread in flight took 40 registers more in here, and the
+        //  search rounds paid for them -- see the claims)
+        const bool hop4 = LINKS && CYTO_WALK_HOP4 && nset >= 32;
+        if (hop4) {
+            const unsigned long long END = 0xFFFFFFFF00000000ull | (uint32_t)fr;
+            for (int q = tid; q < nset; q += WT) {
+                const int k = (int)(uint32_t)ld_sc1(setl + q);
+                unsigned long long *dst = sv.link4 + 4 * (size_t)k;
+                unsigned long long e[4];
+                e[0] = ld_sc1(link + k);
+#pragma unroll
+                for (int d = 1; d < 4; d++) e[d] = (int)(uint32_t)e[d - 1] != fr ? ld_sc1(link + (uint32_t)(e[d - 1] >> 32)) : END;
+#pragma unroll
+                for (int d = 0; d < 4; d++) dst[d] = e[d];       // (behind the loads: a load waits for the stores issued before it)
+            }
+            __syncthreads();
+        }
+        if (w == 0) {
+            // the path, from the sink back to the free row: every lane makes the same loads, lane (hop & 63) keeps the hop, 64 hops are
+            // stored at a time (no store between the loads of a hop: a load returns only after the stores before it are acknowledged)
+#ifdef CYTO_AUG_FIN_SPLIT
+            const long long fs_w0 = wall_clock64();
+#endif
+            int nh = 0, mi = 0, mj = 0;
+            auto rec = [&](int ri, int rj) {
+                if (lane == (nh & 63)) { mi = ri; mj = rj; }
+                nh++;
+                if ((nh & 63) == 0 && nh <= n) { st_sc1(hop_i + nh - 64 + lane, (int32_t)mi); st_sc1(hop_j + nh - 64 + lane, (int32_t)mj); }
+            };
+            int j = sink;
+            int i = uni((int)lid_of(ld_sc1(lbl + sink)));            // (the sink is not settled: it has no link)
+            rec(i, j);
+            if (i != fr) {
+                j = uni(ld_sc1(a.rowsol + i));
+                while (nh < n) {
+                    if (hop4) {                                      // four hops per round trip
+                        unsigned long long e[4];
+#pragma unroll
+                        for (int t = 0; t < 4; t++) e[t] = ld_sc1(sv.link4 + 4 * (size_t)j + t);
+                        bool done = false;
+#pragma unroll
+                        for (int t = 0; t < 4; t++)
+                            if (!done) {
+                                const unsigned long long lk = uni(e[t]);
+                                i = (int)(uint32_t)lk; rec(i, j);
+                                if (i == fr) done = true; else j = (int)(uint32_t)(lk >> 32);
+                            }
+                        if (done) break;
+                    } else if (LINKS) {
+                        const unsigned long long lk = uni(ld_sc1(link + j));
+                        i = (int)(uint32_t)lk; rec(i, j);
+                        if (i == fr) break;
+                        j = (int)(uint32_t)(lk >> 32);
+                    } else {
+                        i = uni((int)lid_of(ld_sc1(lbl + j))); rec(i, j);
+                        if (i == fr) break;
+                        j = uni(ld_sc1(a.rowsol + i));
+                    }
+                }
+            }
+            if (nh > n) nh = n;
+            if (lane < (nh & 63)) { st_sc1(hop_i + (nh & ~63) + lane, (int32_t)mi); st_sc1(hop_j + (nh & ~63) + lane, (int32_t)mj); }
+            if (lane == 0) s.nhop = nh;
+            if (lane == 0 && i != fr) { if (PAR) atomicExch(&pc->err, 1); else s.err = 1; }      // (a path of n hops that has not reached its row: never)
+#ifdef CYTO_AUG_FIN_SPLIT
+            if (lane == 0 && FS_OK) g_fs[batchno - 1][g][FS_WALK] = wall_clock64() - fs_w0;
+#endif
+        } else {
+            // the prices of the columns settled below the end's distance: v[k] += d[k] - D, clamped (prices only decrease)
+            constexpr int UT = WT - 64;
+            const int ne = PAR ? uni(s.nset) : nt;
+            int myscans = 0;
+            for (int q0 = 0; q0 < ne; q0 += 4 * UT) {
+                int k[4], pre[4], cnt = 0;
+                uint32_t dord[4];
+                float vk[4], nv[4];
+                uint64_t m[4];
+                bool up[4];
+                if (PAR) {
+#pragma unroll
+                    for (int t = 0; t < 4; t++) {
+                        const int q = q0 + t * UT + tid - 64;
+                        const unsigned long long e = q < ne ? ld_sc1(setl + q) : ~0ull;
+                        k[t] = (int)(uint32_t)e; dord[t] = (uint32_t)(e >> 32);
+                        up[t] = q < ne && dord[t] < Dord;
+                    }
+                } else {
+#pragma unroll
+                    for (int t = 0; t < 4; t++) { const int q = q0 + t * UT + tid - 64; k[t] = q < ne ? ld_sc1(tch + q) : -1; }
+#pragma unroll
+                    for (int t = 0; t < 4; t++) {
+                        dord[t] = k[t] >= 0 ? (uint32_t)(ld_sc1(lbl + k[t]) >> 32) : 0xFFFFFFFFu;
+                        up[t] = k[t] >= 0 && dord[t] < Dord && is_asg(k[t]);
+                    }
+                }
+#pragma unroll
+                for (int t = 0; t < 4; t++) vk[t] = up[t] ? getv(k[t]) : 0.0f;
+#pragma unroll
+                for (int t = 0; t < 4; t++) {
+                    nv[t] = (vk[t] + ord2f(dord[t])) - D;
+                    myscans += up[t] ? 1 : 0;
+                    up[t] = up[t] && nv[t] < vk[t];                 // (from here on: the price changes)
+                    if (up[t]) { a.v[k[t]] = nv[t]; if (VLDS) s_v[k[t]] = nv[t]; }
+                    if (PAR) { m[t] = __ballot(up[t]); pre[t] = cnt; cnt += __popcll(m[t]); }
+                }
+                if (PAR && cnt) {                                    // the price log: its slots from one atomic per wave
+                    int base = 0;
+                    if (lane == 0) base = atomicAdd(&pc->nplog[par], cnt);
+                    base = uni(base);
+#pragma unroll
+                    for (int t = 0; t < 4; t++)
+                        if (up[t]) { const int e = base + pre[t] + __popcll(m[t] & lanemask_lt()); sv.plog_col[e] = k[t]; sv.plog_val[e] = nv[t]; }
+                }
+            }
+            if (myscans) atomicAdd(&s.scans, myscans);
+        }
+        __syncthreads();
+        FS_LAP(FS_UPDATE)
+        // the new owners, their costs (inside the walk every hop would wait for its cost, an HBM access) and the owner log
+        nhop = uni(s.nhop);
+        for (int q0 = 0; q0 < nhop; q0 += WT) {
+            const int q = q0 + tid;
+            const bool hv = q < nhop;
+            const int i = hv ? ld_sc1(hop_i + q) : 0, j = hv ? ld_sc1(hop_j + q) : 0;
+            if (hv) {
+                a.colsol[j] = i; a.rowsol[i] = j;
+                if (CLDS) s_cs[j] = (uint16_t)i;
+                a.cassign[j] = a.cost[wrow_off(a.rowmap, i, a.ld) + j];
+            }
+            if (PAR) {
+                const uint64_t m = __ballot(hv);
+                if (m) {
+                    int base = 0;
+                    if (lane == 0) base = atomicAdd(&pc->nolog[par], __popcll(m));
+                    base = uni(base);
+                    if (hv) { const int e = base + __popcll(m & lanemask_lt()); sv.olog_col[e] = j; sv.olog_own[e] = i; }
+                }
+            }
+        }
+        if (tid == 0) atomicOr(&asg[sink >> 5], 1u << (sink & 31));
+        FS_SET(FS_HOPS, nhop)
+        FS_LAP(FS_COST)
+    }
+    for (int q0 = 0; q0 < nt; q0 += 4 * WT) {
+        int k[4];
+#pragma unroll
+        for (int t = 0; t < 4; t++) { const int q = q0 + t * WT + tid; k[t] = q < nt ? ld_sc1(tch + q) : -1; }
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+            if (k[t] >= 0) {
+                lbl[k[t]] = ~0ull;
+                atomicAnd(&dirty[k[t] >> 5], ~(1u << (k[t] & 31)));
+                bmin[k[t] >> 6] = ~0ull;
+            }
+    }
+    // (keeping the dense bits across searches was measured: fewer rounds, but more full-row relaxations -- slower)
+    if (s.anydense) for (int q = tid; q < nw32; q += WT) dense[q] = 0;
+    __syncthreads();
+    FS_SET(FS_NTOUCH, nt)
+    FS_LAP(FS_RESET)
+    return (unsigned long long)(uint32_t)nhop | ((unsigned long long)(uint32_t)Pb << 32) | ((unsigned long long)(commit ? 1 : 0) << 48);
+}
+
 template <bool VLDS, bool CLDS, bool PAR, bool EMB = false>
 __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batch) {
     static_assert(!EMB || (PAR && !VLDS), "the embedded form: several searches at once, prices in global memory");
@@ -1454,17 +1791,11 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
     const int nblk = (n + 63) / 64, nw32 = (n + 31) / 32;
     // the search's own arrays: the problem's (one search at a time) or this workgroup's (PAR)
     const int G = PAR ? a.par_groups : 1;
-    const size_t np_ = ((size_t)n + 63) & ~(size_t)63;
     ParCtl *pc = reinterpret_cast<ParCtl *>(a.par);
-    unsigned long long *lbl = PAR ? reinterpret_cast<unsigned long long *>(a.par + 256) + (size_t)g * np_ : a.label;
-    int32_t *tch = PAR ? reinterpret_cast<int32_t *>(a.par + 256 + (size_t)G * np_ * 8) + (size_t)g * np_ : a.touched;
-    int32_t *hop_i = PAR ? reinterpret_cast<int32_t *>(a.par + 256 + (size_t)G * np_ * 12) + (size_t)g * 2 * np_ : a.act0;
-    int32_t *hop_j = PAR ? hop_i + np_ : a.act1;
-    uint32_t *claim = reinterpret_cast<uint32_t *>(a.par + 256 + (size_t)G * np_ * 20);
-    int32_t *plog_col = reinterpret_cast<int32_t *>(claim + np_);
-    float *plog_val = reinterpret_cast<float *>(plog_col + np_);
-    int32_t *olog_col = reinterpret_cast<int32_t *>(plog_val + np_);
-    int32_t *olog_own = olog_col + np_;
+    const SearchView sv(a, PAR, g);
+    unsigned long long *lbl = sv.lbl;
+    int32_t *tch = sv.tch, *plog_col = sv.plog_col, *olog_col = sv.olog_col, *olog_own = sv.olog_own;
+    float *plog_val = sv.plog_val;
     unsigned pgen = 0;
     unsigned long long *bmin = reinterpret_cast<unsigned long long *>(w_smem);
     uint32_t *dirty = reinterpret_cast<uint32_t *>(bmin + nblk);
@@ -1501,7 +1832,7 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
         }
     }
     if (tid == 0) { s.waste = 0; s.stop = 0; }
-    if (tid == 0) { s.T = ~0ull; s.ntouch = 0; s.any[0] = 0; s.any[1] = 0; s.any[2] = 0; s.npk[0] = 0; s.npk[1] = 0; s.npk[2] = 0; s.fail = 0; s.anydense = 0; s.rootdense = 0; s.doroot = 0; s.f = f0; s.err = 0; s.scans = 0; }
+    if (tid == 0) { s.T = ~0ull; s.ntouch = 0; s.any[0] = 0; s.any[1] = 0; s.any[2] = 0; s.npk[0] = 0; s.npk[1] = 0; s.npk[2] = 0; s.fail = 0; s.anydense = 0; s.rootdense = 0; s.doroot = 0; s.f = f0; s.err = 0; s.scans = 0; s.nset = 0; }
     __syncthreads();
     auto getv = [&](int j) -> float { return VLDS ? s_v[j] : ld_sc1(a.v + j); };
     auto getcs = [&](int j) -> int {
@@ -1514,6 +1845,11 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
     long long t_rounds = 0, t_verify = 0, t_finish = 0, t_triv = 0, t_mark = wall_clock64();
 
 #define AUG_LAP(acc) { const long long now_ = wall_clock64(); acc += now_ - t_mark; t_mark = now_; }
+#ifdef CYTO_AUG_FIN_SPLIT
+    long long fs_mark = 0;
+    if (tid == 0) s.st_col[63] = 0;                              // (FS_COUNT: the settled columns of the search; PAR never stages one-edge results)
+    __syncthreads();
+#endif
 
     // a relaxation in two halves: the offer (column `col` is offered the ordered distance `co` by row `row`; returns the label
     // it replaced or lost against) and what follows from it -- first touch, dirty column, best unassigned column
@@ -1902,99 +2238,20 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
         // ---- the search has ended at s.T: [PAR: claim, find the conflict-free prefix of the batch;] price update, path flip, reset ----
         const unsigned long long Tk = active ? s.T : ~0ull;
         if (!PAR && Tk == ~0ull) { if (tid == 0) s.err = 1; __syncthreads(); break; }
-        const uint32_t Dord = (uint32_t)(Tk >> 32);
-        const float D = ord2f(Dord);
-        const int sink = (int)lid_of(Tk);
-        const int nt = active ? s.ntouch : 0;
-        bool commit = true;
-        int Pb = G;
+        // (search_end, out of line; PAR: it meets the launch at one grid barrier)
+        const unsigned long long er = uni(search_end<VLDS, CLDS, PAR>(batch, (lds_aug_t *)&s, (lds_u64_t *)w_smem, g, fr, batchno, pgen, active ? 1 : 0));
+        if (PAR) pgen++;
+        const bool commit = (er >> 48) & 1;
+        const int Pb = (int)((er >> 32) & 0xFFFFu);
         const int par = batchno & 1;
-        if (PAR) {
-            const bool have = Tk != ~0ull;
-            if (active && !have && tid == 0) atomicExch(&pc->err, 1);
-            // every column this search settled (label below its end's) and its sink: claimed with (batch, workgroup) -- the atomic max
-            // keeps the LOWEST workgroup of the LATEST batch
-            const uint32_t key = ((uint32_t)batchno << 8) | (uint32_t)(255 - g);
-            if (have) {
-                for (int q = tid; q < nt; q += WT) {
-                    const int k = ld_sc1(tch + q);
-                    if (lv_of(ld_sc1(lbl + k)) < lv_of(Tk) && is_asg(k)) atomicMax(claim + k, key);
-                }
-                if (tid == 0) atomicMax(claim + sink, key);
-            }
-            if (tid == 0) s.conflict = 0;
-            par_barrier(pc, G, pgen);
-            if (have) {
-                int c = 0;
-                for (int q = tid; q < nt; q += WT) {
-                    const int k = ld_sc1(tch + q);
-                    if (lv_of(ld_sc1(lbl + k)) < lv_of(Tk) && is_asg(k) && ld_sc1(claim + k) != key) c = 1;
-                }
-                if (tid == 0 && ld_sc1(claim + sink) != key) c = 1;
-                if (c) s.conflict = 1;
-            }
-            __syncthreads();
-            if (tid == 0 && active && (s.conflict || !have)) atomicMin(&pc->P[par], g);
-            par_barrier(pc, G, pgen);
-            Pb = uni(ld_sc1(&pc->P[par]));
-            Pb = Pb < G ? Pb : G;
-            // (the other parity's words are free: their last readers passed this batch's first barrier)
-            if (g == 0 && tid == 0) { st_sc1(&pc->P[par ^ 1], PAR_GMAX + 1); st_sc1(&pc->nplog[par ^ 1], 0); st_sc1(&pc->nolog[par ^ 1], 0); }
-            commit = active && have && g < Pb;
-            if (active && !commit) c_discarded++;
-        }
-        if (commit) {
-            int myscans = 0;
-            for (int q = tid; q < nt; q += WT) {
-                const int k = ld_sc1(tch + q);
-                const uint32_t dord = (uint32_t)(ld_sc1(lbl + k) >> 32);
-                if (dord < Dord && is_asg(k)) {
-                    const float vk = getv(k);
-                    const float nv = (vk + ord2f(dord)) - D;
-                    if (nv < vk) {
-                        a.v[k] = nv; if (VLDS) s_v[k] = nv;
-                        if (PAR) { const int e = atomicAdd(&pc->nplog[par], 1); plog_col[e] = k; plog_val[e] = nv; }
-                    }
-                    myscans++;
-                }
-            }
-            if (myscans) atomicAdd(&s.scans, myscans);
-            if (tid == 0) {
-                // (the new owner entries' costs are fetched afterwards, by everybody: inside this walk every hop waited for its cost --
-                //  an HBM access, and loads return in order -- before the next hop's label arrived: 0.7 us per hop, 37 824 hops on a c4 chunk)
-                int j = sink, nh = 0;
-                for (;;) {
-                    const int i = (int)lid_of(ld_sc1(lbl + j));
-                    const int jn = ld_sc1(a.rowsol + i);
-                    a.colsol[j] = i; a.rowsol[i] = j;
-                    st_sc1(hop_i + nh, (int32_t)i); st_sc1(hop_j + nh, (int32_t)j); nh++;
-                    if (CLDS) s_cs[j] = (uint16_t)i;
-                    c_hops++;
-                    if (i == fr) break;
-                    j = jn;
-                }
-                s.nhop = nh;
-                atomicOr(&asg[sink >> 5], 1u << (sink & 31));
-            }
-            __syncthreads();
-            for (int q = tid; q < s.nhop; q += WT) {
-                const int i = ld_sc1(hop_i + q), j = ld_sc1(hop_j + q);
-                a.cassign[j] = a.cost[wrow_off(a.rowmap, i, a.ld) + j];
-                if (PAR) { const int e = atomicAdd(&pc->nolog[par], 1); olog_col[e] = j; olog_own[e] = i; }
-            }
-        }
-        for (int q = tid; q < nt; q += WT) {
-            const int k = ld_sc1(tch + q);
-            lbl[k] = ~0ull;
-            atomicAnd(&dirty[k >> 5], ~(1u << (k & 31)));
-            bmin[k >> 6] = ~0ull;
-        }
-        // (keeping the dense bits across searches was measured: fewer rounds, but more full-row relaxations -- slower)
-        if (s.anydense) for (int q = tid; q < nw32; q += WT) dense[q] = 0;
-        __syncthreads();
-        if (tid == 0) { if (commit) c_relax += s.scans; s.scans = 0; s.T = ~0ull; s.ntouch = 0; s.anydense = 0; s.rootdense = 0; s.f = f + 1; }
+        c_hops += (long long)(uint32_t)er;
+        if (PAR && active && !commit) c_discarded++;
+        if (tid == 0) { if (commit) c_relax += s.scans; s.scans = 0; s.T = ~0ull; s.ntouch = 0; s.nset = 0; s.anydense = 0; s.rootdense = 0; s.f = f + 1; }
         f++;
         __syncthreads();
+#ifdef CYTO_AUG_FIN_SPLIT
+        if (PAR && tid == 0) fs_mark = wall_clock64();
+#endif
         if (PAR) {
             // the batch's changes, into this workgroup's copies (its own included: harmless); then the next batch
             par_barrier(pc, G, pgen);
@@ -2007,6 +2264,7 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
                 atomicOr(&asg[col >> 5], 1u << (col & 31));
             }
             __syncthreads();
+            FS_LAP(FS_WAIT3)
             const int left = numfree - fbase;
             fbase += Pb < left ? Pb : left;                       // (Pb >= 1: the first search of a batch never conflicts)
             if (Pb < 1) perr = 1;
@@ -2023,6 +2281,11 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
                 }
                 par_barrier(pc, G, pgen);
             }
+            FS_LAP(FS_REPAIR)
+#ifdef CYTO_AUG_FIN_SPLIT
+            FS_SET(FS_SETTLED, s.st_col[63])
+            if (tid == 0) s.st_col[63] = 0;
+#endif
             batchno++; c_batches++;
         }
         AUG_LAP(t_finish)
@@ -2636,11 +2899,11 @@ int wide_solve_batch(const WidePlan &pl, const std::vector<SolveJob> &jobs, hipS
             const size_t np_ = ((size_t)n + 63) & ~(size_t)63;
             wa.par = j.state->as<char>() + par_off;
             CYTO_HIP(hipMemsetAsync(wa.par, 0, 256, stream));                                            // the control block ...
-            const int p_init[2] = {WIDE_PAR_GMAX + 1, WIDE_PAR_GMAX + 1};
-            CYTO_HIP(hipMemcpyAsync(wa.par + 8, p_init, sizeof p_init, hipMemcpyHostToDevice, stream));   // ... P[0], P[1]: "no conflict"
+            // ... P[0], P[1]: "no conflict"  (a fill, not a copy from a local: a copy had the host wait here, through the column pass,
+            //  and what follows -- memsets, wide_rt, the first round launches -- was enqueued onto an idle chip)
+            CYTO_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(wa.par + 8), WIDE_PAR_GMAX + 1, 2, stream));
             CYTO_HIP(hipMemsetAsync(wa.par + 256, 0xFF, (size_t)parg * np_ * 8, stream));                  // every search's labels: all-ones
             CYTO_HIP(hipMemsetAsync(wa.par + 256 + (size_t)parg * np_ * 20, 0, np_ * 4, stream));          // the claim words
-            CYTO_HIP(hipStreamSynchronize(stream));                                                         // (p_init is a local)
         }
         // the post-column-reduction prices: snapshot for the reduction transfer AND the raw cost of every owner entry
         CYTO_HIP(hipMemcpyAsync(wa.cassign, wa.v, nT, hipMemcpyDeviceToDevice, stream));
@@ -2726,3 +2989,17 @@ void wide_info(cyto_lap_info *info, const LapStatus &h) {
 }  // namespace cyto
 
 extern "C" long long cyto_wide_embedded_solves(void) { return cyto::g_embedded_solves.load(); }
+
+#ifdef CYTO_AUG_FIN_SPLIT
+// the batch ends of the solves since the last call, by parts: out[batch][workgroup][part] in 100-MHz ticks (tools/fin_split.py); then cleared
+extern "C" int cyto_wide_fin_split(long long *out, int *max_batches, int *groups, int *parts) {
+    using namespace cyto;
+    *max_batches = FS_MAXB; *groups = FS_G; *parts = FS_NP;
+    if (!out) return 0;
+    if (hipDeviceSynchronize() != hipSuccess) return 5;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fs), sizeof(long long) * FS_MAXB * FS_G * FS_NP) != hipSuccess) return 5;
+    void *p = nullptr;
+    if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_fs)) != hipSuccess || hipMemset(p, 0, sizeof(long long) * FS_MAXB * FS_G * FS_NP) != hipSuccess) return 5;
+    return 0;
+}
+#endif
