@@ -111,6 +111,14 @@ int cyto_cache_peek(size_t bytes, void *host_out, int device_id);
  *   info          timing/work counters                           (out; may be NULL)
  *   stream        hipStream_t to launch on, NULL = the device's default stream
  * Results are bit-identical to oracle/jv_oracle.c for the same dtype (tests/test_lap_gpu.py).
+ *
+ * Range of the costs.  Any finite float32 costs, subnormal values and -0.0 included (-0.0 is the cost 0), and the results depend on
+ * the matrix through its values only: a matrix scaled by a power of two, without under- or overflow, gives the same indices and the
+ * duals scaled by it, bit for bit.  Every intermediate (a dual, a reduced cost, a distance) stays finite when
+ * 2 * n * max|c| < 2^127; beyond that bound -- costs near FLT_MAX, where c - v can overflow -- the result is unspecified.  The float64
+ * solve accepts any finite float64 costs under the same bound in its own format (2^1023); its warm start narrows to float32 and falls
+ * back to the cold start when the narrowed image is not finite.  Pinned by tests/test_lap_ranges_*.py against the oracle, which
+ * tests/test_lap_ranges_cpu.py pins against an exact solver over the same range.
  */
 typedef struct {
     double ms_colred;        /* HIP-event time of the column-reduction kernels */
