@@ -21,6 +21,8 @@ CYTO_ERR_UNSUPPORTED = 7
 CYTO_DTYPE_F32, CYTO_DTYPE_F64, CYTO_DTYPE_U16, CYTO_DTYPE_U8, CYTO_DTYPE_I32, CYTO_DTYPE_I64 = range(6)
 # cyto_mtx_info.reason with CYTO_ERR_UNSUPPORTED (include/cytohip.h: CYTO_MTX_ERR_*)
 CYTO_MTX_ERR_FRACTION, CYTO_MTX_ERR_NONFINITE, CYTO_MTX_ERR_MAGNITUDE, CYTO_MTX_ERR_SQUARE, CYTO_MTX_ERR_IO = range(2, 7)
+# cyto_csv_info.reason with CYTO_ERR_UNSUPPORTED (include/cytohip.h: CYTO_CSV_ERR_*)
+CYTO_CSV_ERR_FRACTION, CYTO_CSV_ERR_NONFINITE, CYTO_CSV_ERR_MAGNITUDE, CYTO_CSV_ERR_IO = 2, 3, 4, 6
 
 
 class CytoHipError(RuntimeError):
@@ -82,6 +84,13 @@ class MtxInfo(ctypes.Structure):
     _fields_ = [("nnz", ctypes.c_int64), ("bytes", ctypes.c_int64), ("blocks", ctypes.c_int64), ("field", ctypes.c_int32),
                 ("reason", ctypes.c_int32), ("ms_upload", ctypes.c_double), ("ms_kernels", ctypes.c_double),
                 ("ms_download", ctypes.c_double), ("ms_write", ctypes.c_double)]
+
+
+class CsvInfo(ctypes.Structure):
+    """cyto_csv_info (include/cytohip.h)."""
+    _fields_ = [("bytes", ctypes.c_int64), ("blocks", ctypes.c_int64), ("reason", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("ms_upload", ctypes.c_double), ("ms_kernels", ctypes.c_double), ("ms_download", ctypes.c_double),
+                ("ms_write", ctypes.c_double)]
 
 
 class MtxReadInfo(ctypes.Structure):
@@ -202,6 +211,10 @@ def lib():
         L.cyto_mtx_write.restype = ctypes.c_int
         L.cyto_mtx_format_entries.argtypes = [vp, vp, vp, i32, i64, vp, vp]
         L.cyto_mtx_format_entries.restype = ctypes.c_int
+        L.cyto_csv_write.argtypes = [ctypes.c_char_p, i64, i64, vp, i64, i32, vp, i64, vp, i64, vp, vp, i64, i32, ctypes.POINTER(CsvInfo)]
+        L.cyto_csv_write.restype = ctypes.c_int
+        L.cyto_csv_format_fields.argtypes = [vp, i32, i64, vp, i64, vp]
+        L.cyto_csv_format_fields.restype = ctypes.c_int
         L.cyto_mtx_read.argtypes = [ctypes.c_char_p, i64, i64, i64, i64, i32, vp, i64, i32, ctypes.POINTER(MtxReadInfo)]
         L.cyto_mtx_read.restype = ctypes.c_int
         L.cyto_mtx_parse_entries.argtypes = [vp, i64, vp, i32, i64, i64, vp, vp, vp, vp, vp]

@@ -13,15 +13,12 @@
 // The body is formatted in blocks of whole genes that fit a bounded device buffer; block k is downloaded into one of two pinned
 // buffers while block k + 1 is formatted and block k - 1 is written to the file.
 // fmt_line is the one formatter: the count pass, the format pass and the host (cyto_mtx_format_entries) all call it.
-#include "cyto_common.h"
+#include "text_write.h"
 
-#include <errno.h>
 #include <fcntl.h>
 #include <math.h>
-#include <unistd.h>
 
 #include <algorithm>
-#include <chrono>
 #include <vector>
 
 namespace {
@@ -35,37 +32,6 @@ constexpr int MAX_VALUE = 21;                            // "-9.007199254740991E
 constexpr int MAX_LINE = 10 + 1 + 10 + 1 + MAX_VALUE + 1;   // G and C are below 2^31: at most 10 digits each
 constexpr int STAGE = SEG * MAX_LINE + 16;               // a segment's text, shifted by up to 15 bytes
 constexpr int64_t DEFAULT_BLOCK = int64_t(32) << 20;
-
-__host__ __device__ inline int ndigits32(uint32_t v) {
-    return v < 10u ? 1 : v < 100u ? 2 : v < 1000u ? 3 : v < 10000u ? 4 : v < 100000u ? 5 : v < 1000000u ? 6 : v < 10000000u ? 7
-         : v < 100000000u ? 8 : v < 1000000000u ? 9 : 10;
-}
-
-__host__ __device__ inline int ndigits64(uint64_t v) {
-    if (v <= 0xffffffffull) return ndigits32((uint32_t)v);
-    int n = 10;
-    for (uint64_t p = 10000000000ull; n < 20 && v >= p; p *= 10) n++;   // (p wraps only after n has reached 20)
-    return n;
-}
-
-// o[0, nd) := the nd decimal digits of v (nd = ndigits64(v)); 32-bit arithmetic once what is left fits.
-__host__ __device__ inline void put_digits(uint8_t *o, uint64_t v, int nd) {
-    int i = nd;
-    while (v > 0xffffffffull) {
-        const uint64_t q = v / 1000000000ull;
-        uint32_t r = (uint32_t)(v - q * 1000000000ull);
-        for (int k = 0; k < 9; k++) {
-            o[--i] = (uint8_t)('0' + r % 10u);
-            r /= 10u;
-        }
-        v = q;
-    }
-    uint32_t w = (uint32_t)v;
-    while (i > 0) {
-        o[--i] = (uint8_t)('0' + w % 10u);
-        w /= 10u;
-    }
-}
 
 // A value as the formatter takes it.  status: 0 a non-zero inside the grammar, 1 a zero (not written), else CYTO_MTX_ERR_*.
 struct Val {
@@ -162,29 +128,6 @@ template <bool WRITE> __host__ __device__ inline int fmt_line(uint8_t *o, uint64
     return n + 1;
 }
 
-// Exclusive scan of one value per thread across the workgroup; *total: the sum.  Every thread must call it.
-template <typename V> __device__ __forceinline__ V wg_scan(V v, V *total) {
-    __shared__ V wsum[WG / 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    V x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const V y = __shfl_up(x, off, 64);
-        if (lane >= off) x += y;
-    }
-    if (lane == 63) wsum[w] = x;
-    __syncthreads();
-    V before = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < WG / 64; i++) {
-        before += i < w ? wsum[i] : V(0);
-        tot += wsum[i];
-    }
-    __syncthreads();                                    // (wsum is reused by the next call)
-    *total = tot;
-    return before + x - v;
-}
-
 // A workgroup per gene g.  seg_off[g * nseg + s] := the bytes of gene g's lines before segment s; row_bytes[g], row_nnz[g] := its
 // totals; *flags |= 1 << CYTO_MTX_ERR_* for every kind of value outside the grammar.
 template <typename T>
@@ -205,7 +148,7 @@ __global__ __launch_bounds__(WG) void mtx_count(const T *X, int64_t ldx, const i
             else if (v.status > 1) bad |= 1 << v.status;
         }
         int tot;
-        wg_scan(packed, &tot);
+        wg_scan<WG>(packed, &tot);
         if (threadIdx.x == 0) seg_off[g * nseg + s] = run;
         run += tot & 0xffff;
         nz += tot >> 16;
@@ -223,8 +166,8 @@ __global__ __launch_bounds__(WG) void mtx_scan(const int64_t *row_bytes, const i
     for (int64_t g0 = 0; g0 < G; g0 += WG) {
         const int64_t g = g0 + threadIdx.x;
         int64_t tot, tnz;
-        const int64_t ex = wg_scan<int64_t>(g < G ? row_bytes[g] : 0, &tot);
-        wg_scan<int64_t>(g < G ? row_nnz[g] : 0, &tnz);
+        const int64_t ex = wg_scan<WG, int64_t>(g < G ? row_bytes[g] : 0, &tot);
+        wg_scan<WG, int64_t>(g < G ? row_nnz[g] : 0, &tnz);
         if (g < G) row_off[g] = carry + ex;
         carry += tot;
         nz += tnz;
@@ -258,7 +201,7 @@ __global__ __launch_bounds__(WG) void mtx_format(const T *X, int64_t ldx, const 
         mine += len[k];
     }
     int tot;
-    const int ex = wg_scan(mine, &tot);
+    const int ex = wg_scan<WG>(mine, &tot);
     if (tot == 0) return;
     const int64_t dst = row_off[g] - base + seg_off[g * nseg + s];
     const int shift = (int)(dst & 15);                  // stage[p] is byte (dst - shift + p) of out: chunks line up
@@ -281,43 +224,6 @@ __global__ __launch_bounds__(WG) void mtx_format(const T *X, int64_t ldx, const 
             for (int b = lo < shift ? shift : lo; b < (hi < span ? hi : span); b++) o[b] = stage[b];
         }
     }
-}
-
-// The output file: removed again unless the whole of it was written.
-struct OutFile {
-    int fd = -1;
-    const char *path = nullptr;
-    bool keep = false;
-    ~OutFile() {
-        if (fd < 0) return;
-        close(fd);
-        if (!keep) unlink(path);
-    }
-    bool write_all(const void *buf, size_t n) {
-        const char *q = static_cast<const char *>(buf);
-        while (n > 0) {
-            const ssize_t r = write(fd, q, n);
-            if (r < 0 && errno == EINTR) continue;
-            if (r <= 0) return false;
-            q += r;
-            n -= (size_t)r;
-        }
-        return true;
-    }
-};
-
-double ms_since(std::chrono::steady_clock::time_point t) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
-}
-
-size_t dtype_size(int dt) {
-    switch (dt) {
-    case CYTO_DTYPE_U8: return 1;
-    case CYTO_DTYPE_U16: return 2;
-    case CYTO_DTYPE_F32: case CYTO_DTYPE_I32: return 4;
-    case CYTO_DTYPE_F64: case CYTO_DTYPE_I64: return 8;
-    }
-    return 0;
 }
 
 // CALL with T bound to the element type of CYTO_DTYPE_* dt

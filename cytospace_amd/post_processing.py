@@ -1,9 +1,10 @@
 """Output writers of the reference: `save_results`
 (/root/reference/cytospace/post_processing/post_processing.py:10-116) and the unassigned-spot table written by
 main_cytospace (/root/reference/cytospace/cytospace.py:686-694).  Host code (pandas), same file names, columns and
-ordering, so a run of this package can be post-processed by the same downstream scripts; with a device, the one large file
-(assigned_expression/matrix.mtx) is formatted on the GPU by write_mtx_device, byte for byte what scipy writes.  Written from the format, not
-from the reference's statements: tests/golden/gv12_* holds files the reference itself wrote for the same inputs.
+ordering, so a run of this package can be post-processed by the same downstream scripts; with a device, the one large file of a run
+(assigned_expression/matrix.mtx, or new_scRNA.csv with place-holders) is formatted on the GPU by write_mtx_device / write_csv_device,
+byte for byte what scipy / pandas writes.  Written from the format, not from the reference's statements: tests/golden/gv12_* holds
+files the reference itself wrote for the same inputs.
 """
 import math
 import os
@@ -143,10 +144,153 @@ def write_mtx_device(path, matrix_or_frame, columns, device_id=0, block_bytes=0,
     return info if return_info else None
 
 
+# numpy dtype -> (the dtype uploaded, CYTO_DTYPE_*) of write_csv_device; every other dtype is written by pandas.  No narrowing here:
+# the text depends on the dtype's kind alone, and choosing a narrower upload would be a host pass over the matrix.
+_CSV_DTYPES = _MTX_DTYPES
+_CSV_REFUSALS = {_lib.CYTO_CSV_ERR_FRACTION: "non-integer value", _lib.CYTO_CSV_ERR_NONFINITE: "non-finite value",
+                 _lib.CYTO_CSV_ERR_MAGNITUDE: "magnitude", _lib.CYTO_CSV_ERR_IO: "io"}
+
+
+class _Rows(list):
+    """The file object of a csv.writer that keeps each row's text apart (the writer calls write() once per row)."""
+    write = list.append
+
+
+def _csv_labels(labels):
+    """labels as the strings csv.writer gets from pandas, or None: strings stay, integers are their digits; whatever pandas formats
+    by rules of its own (floats, dates, missing values, tuples of a MultiIndex) is not taken."""
+    out = []
+    for v in labels:
+        if isinstance(v, str):
+            out.append(v)
+        elif isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)):
+            out.append(str(int(v)))
+        else:
+            return None
+    return out
+
+
+def csv_header_and_labels(index_labels, column_labels, index_name=None):
+    """What the host formats of DataFrame.to_csv's text, by pandas' own means (csv.writer, QUOTE_MINIMAL, '\\n' line ends):
+    (the header line, the genes' labels each with its trailing ',' as one bytes object, int64 offsets [G + 1] into it); None when a
+    label is neither a string nor an integer.  An empty label stays empty: pandas quotes it only in a row without other fields."""
+    import csv
+    rows, cols = _csv_labels(index_labels), _csv_labels(column_labels)
+    name = "" if index_name is None else _csv_labels([index_name])
+    if rows is None or cols is None or name is None:
+        return None
+    sink = _Rows()
+    w = csv.writer(sink, lineterminator="\n", delimiter=",", quoting=csv.QUOTE_MINIMAL, doublequote=True, escapechar=None, quotechar='"')
+    w.writerow([name if name == "" else name[0]] + cols)
+    header = sink.pop().encode("utf-8")
+    w.writerows((r, "") for r in rows)                    # "<label>,\n": the second, empty field keeps an empty label unquoted
+    parts = [t[:-1].encode("utf-8") for t in sink]
+    off = np.zeros(len(parts) + 1, np.int64)
+    np.cumsum([len(p) for p in parts], out=off[1:])
+    return header, b"".join(parts), off
+
+
+def write_csv_device(path, matrix_or_frame, columns, index_labels=None, column_labels=None, index_name=None, device_id=0, block_bytes=0,
+                     return_info=False):
+    """out = frame.iloc[:, columns]; out.index = index_labels; out.columns = column_labels; out.index.name = index_name;
+    out.to_csv(path) -- with the value fields formatted on the GPU (C ABI: cyto_csv_write; csrc/csv.hip): the same bytes, and the
+    selected genes x cells frame is never built on the host.  matrix_or_frame: genes x cells, a DataFrame or a 2-D array; columns:
+    the positions (not labels) of the cells to write, in file order, repeats and negative positions allowed.  index_labels (G),
+    column_labels (len(columns)) and index_name default to the frame's own (an array: range(...) labels, no name); index_name=""
+    writes no name where the frame has one (pandas' header is the same for "" and for None).  block_bytes: the
+    most text per slab of genes (0: the library's default; tests force many slabs with it).
+
+    The host formats the header line and the gene labels (pandas' quoting applies to them), the device every value: integer dtypes
+    as decimals, float32 / float64 integers as "<digits>.0" ("-0.0" for a negative zero).  What the device does not format is
+    written by pandas itself (DESIGN.md 4.1d'), after whatever was at `path` has been removed: a real value that is not an integer
+    below 2^53 (2^24 for float32) -- found by the device while it counts, also in a late slab --, a dtype other than int8..int64 /
+    uint8 / uint16 / float32 / float64, selected columns of more than one dtype, duplicate column labels in the source frame, labels
+    that are neither strings nor integers, an empty result, a path that is not a str, a file that cannot be created or written.
+
+    return_info: also return a dict -- "path" ("device" or "pandas"), for a fallback "reason", and for the device "bytes", "blocks"
+    and the phase times in seconds: labels_s (the host's header and labels), library_s (the whole cyto_csv_write call: device and
+    pinned allocations and their release besides the next four), upload_s, kernels_s, download_s (the three are device times and
+    overlap write_s), write_s, total_s."""
+    import ctypes
+    import time
+    t0 = time.perf_counter()
+    info = {"path": "device"}
+    frame = matrix_or_frame if isinstance(matrix_or_frame, pd.DataFrame) else None
+    if frame is None:
+        matrix_or_frame = np.asarray(matrix_or_frame)
+        if matrix_or_frame.ndim != 2:
+            raise ValueError("write_csv_device needs a 2-D matrix")
+    G, N = matrix_or_frame.shape
+    columns = np.asarray(columns, dtype=np.int64).reshape(-1)
+    if columns.size and (columns.min() < -N or columns.max() >= N):
+        raise IndexError("positional indexers are out-of-bounds")
+    columns = np.ascontiguousarray(np.where(columns < 0, columns + N, columns))
+    C = len(columns)
+    if index_labels is None:
+        index_labels = frame.index if frame is not None else range(G)
+    if column_labels is None:
+        column_labels = frame.columns[columns] if frame is not None else columns
+    if index_name is None and frame is not None:
+        index_name = frame.index.name
+    if len(index_labels) != G or len(column_labels) != C:
+        raise ValueError("write_csv_device: index_labels / column_labels do not fit the selection")
+
+    def refuse(reason):
+        info.update(path="pandas", reason=reason)
+        if isinstance(path, str) and os.path.lexists(path) and not os.path.isdir(path):
+            os.remove(path)
+        out = frame.iloc[:, columns] if frame is not None else pd.DataFrame(matrix_or_frame[:, columns])
+        out.index = pd.Index(index_labels).rename(index_name)
+        out.columns = column_labels
+        out.to_csv(path)
+        info["total_s"] = time.perf_counter() - t0
+        return info if return_info else None
+
+    if not isinstance(path, str):
+        return refuse("not a path")
+    if G == 0 or C == 0:
+        return refuse("empty")
+    x, picked = matrix_or_frame, columns
+    if frame is not None:
+        if not frame.columns.is_unique:
+            return refuse("duplicate labels")
+        if len(frame.dtypes.unique()) > 1:                   # pandas formats each column by its own dtype ("1,1.0")
+            used = np.unique(columns)
+            if len(frame.dtypes.iloc[used].unique()) > 1:
+                return refuse("mixed dtypes")
+            x, picked = frame.iloc[:, used], np.ascontiguousarray(np.searchsorted(used, columns))
+            N = len(used)
+        if str(x.dtypes.iloc[0]) not in _CSV_DTYPES:         # (before to_numpy: a sparse or extension dtype is not made dense)
+            return refuse(f"dtype {x.dtypes.iloc[0]}")
+        x = x.to_numpy()
+    if x.dtype.name not in _CSV_DTYPES:
+        return refuse(f"dtype {x.dtype}")
+    t = time.perf_counter()
+    text = csv_header_and_labels(index_labels, column_labels, index_name)
+    info["labels_s"] = time.perf_counter() - t
+    if text is None:
+        return refuse("labels")
+    header, labels, off = text
+    to, code = _CSV_DTYPES[x.dtype.name]
+    x = np.ascontiguousarray(x, dtype=to)                    # (a copy for int8 / int16 and for a frame held column-major)
+    ci = _lib.CsvInfo()
+    t = time.perf_counter()
+    st = _lib.lib().cyto_csv_write(path.encode(), G, N, x.ctypes.data, N, code, picked.ctypes.data, C, header, len(header), labels,
+                                   off.ctypes.data, int(block_bytes), device_id, ctypes.byref(ci))
+    info["library_s"] = time.perf_counter() - t
+    if st == _lib.CYTO_ERR_UNSUPPORTED:                                      # nothing is left at `path`
+        return refuse(_CSV_REFUSALS.get(ci.reason, str(ci.reason)))
+    _lib.check(st)
+    info.update(bytes=ci.bytes, blocks=ci.blocks, upload_s=ci.ms_upload / 1e3, kernels_s=ci.ms_kernels / 1e3,
+                download_s=ci.ms_download / 1e3, write_s=ci.ms_write / 1e3)
+    info["total_s"] = time.perf_counter() - t0
+    return info if return_info else None
+
+
 def save_results(output_path, output_prefix, cell_ids_selected, all_cells_save, assigned_locations,
                  cell_type_data, sampling_method, single_cell, device_id=None):
-    """post_processing.py:10-116, same arguments, and device_id: None writes matrix.mtx on the host (scipy); a device number has
-    write_mtx_device write it (the same bytes).  Writes
+    """post_processing.py:10-116, same arguments, and device_id: None writes matrix.mtx / new_scRNA.csv on the host (scipy / pandas);
+    a device number has write_mtx_device / write_csv_device write them (the same bytes).  Writes
       <prefix>assigned_locations.csv
       <prefix>assigned_expression/{genes.tsv, barcodes.tsv, matrix.mtx}     (sampling_method "duplicates")
       <prefix>new_scRNA.csv                                                 ("place_holders": the generated cells)
@@ -182,6 +326,12 @@ def save_results(output_path, output_prefix, cell_ids_selected, all_cells_save, 
             genes.to_csv(os.path.join(out_dir, "genes.tsv"), sep="\t", header=False, index=False)
             pd.Index(df.UniqueCID).to_frame().to_csv(os.path.join(out_dir, "barcodes.tsv"), sep="\t", header=False, index=False)
             write_mtx_device(os.path.join(out_dir, "matrix.mtx"), all_cells_save, positions, device_id=device_id)
+    elif device_id is not None and all_cells_save.columns.is_unique:
+        positions = np.flatnonzero(~all_cells_save.columns.isin(cell_type_data.index))     # the generated cells, without their frame
+        write_csv_device(os.path.join(output_path, f"{output_prefix}new_scRNA.csv"), all_cells_save, positions,
+                         index_labels=_strip("GENE_", all_cells_save.index.astype(str)),
+                         column_labels=_strip("CELL_", all_cells_save.columns[positions].astype(str)), index_name="",
+                         device_id=device_id)          # (the host branch's list of labels drops the index's name: none here either)
     else:
         generated = all_cells_save.loc[:, ~all_cells_save.columns.isin(cell_type_data.index)]
         generated.index = _strip("GENE_", generated.index.astype(str))

@@ -559,6 +559,44 @@ int cyto_mtx_write(const char *path, int64_t G, int64_t N, const void *x, int64_
 int cyto_mtx_format_entries(const int64_t *rows, const int64_t *cols, const void *values, int dtype, int64_t n, char *out,
                             int64_t *offsets);
 
+/* ---- the place-holder expression table, <prefix>new_scRNA.csv (cytospace_amd.post_processing.write_csv_device): what pandas'
+ * DataFrame.to_csv writes for the genes x selected-cells frame, byte for byte, the value fields formatted on the device (DESIGN.md
+ * 4.1d').  x: G x N host matrix (ldx) of any CYTO_DTYPE_*; cols: C source columns in [0, N), in file order, repeats allowed;
+ * G, C < 2^31.  The file is `header` (header_len bytes: the whole first line with its '\n', the caller's: quoting rules apply to it),
+ * then per gene g the bytes labels[label_off[g], label_off[g + 1]) (the caller's too: the quoted label WITH its trailing ','), the C
+ * values separated by ',' and a '\n'.  An integer type's value is its decimal digits; a float32 / float64 value that is an integer is
+ * the integer's digits and ".0", with a '-' in front when the sign bit is set ("-0.0").  The source rows go up in slabs of whole genes
+ * (two streams, two device and two pinned buffers: slab k + 1 is formatted while slab k is written), so device memory stays bounded
+ * whatever G is; block_bytes: the most text per slab, by the longest field the type can have (0: 32 MiB; a gene with more stands alone).
+ * CYTO_ERR_BAD_ARG, before any device is touched: a null pointer, G, N, C <= 0, header_len < 0, block_bytes < 0, ldx < N, a
+ * column outside [0, N), an unknown dtype, label_off negative or decreasing.
+ * CYTO_ERR_UNSUPPORTED: info->reason = CYTO_CSV_ERR_*, and nothing is left at `path` (not even a file that was there before): the
+ * caller has pandas write the file.  A value is refused while the device counts its slab, so a late one removes a partial file. */
+enum {
+    CYTO_CSV_ERR_FRACTION = 2,    /* a real value with a fractional part */
+    CYTO_CSV_ERR_NONFINITE = 3,   /* NaN or +-inf */
+    CYTO_CSV_ERR_MAGNITUDE = 4,   /* a real value of magnitude >= 2^53 (float32: >= 2^24) */
+    CYTO_CSV_ERR_IO = 6           /* open() or write() failed */
+};
+typedef struct cyto_csv_info {
+    int64_t bytes;                /* bytes of the file, header included */
+    int64_t blocks;               /* slabs the body took */
+    int32_t reason;               /* CYTO_CSV_ERR_* with CYTO_ERR_UNSUPPORTED, else 0 */
+    int32_t reserved;
+    double ms_upload;             /* the slabs' source rows, label offsets and label bytes, host to device (device events); the column
+                                     list goes up once before the first slab and is not counted */
+    double ms_kernels;            /* count, scan and format launches (device events) */
+    double ms_download;           /* the slabs' text into pinned memory (device events; overlaps the other phases) */
+    double ms_write;              /* write() calls */
+} cyto_csv_info;
+int cyto_csv_write(const char *path, int64_t G, int64_t N, const void *x, int64_t ldx, int x_dtype, const int64_t *cols, int64_t C,
+                   const char *header, int64_t header_len, const char *labels, const int64_t *label_off, int64_t block_bytes,
+                   int device_id, cyto_csv_info *info);
+/* The field formatter alone, on the host (a test hook): the text of values[i] (CYTO_DTYPE_* dtype), without a separator, is
+ * out[sum of lens[0 .. i), + lens[i]).  cap: the bytes of out, at least 20 * n.  CYTO_ERR_UNSUPPORTED at the first real value outside
+ * the device grammar (lens[i] := -CYTO_CSV_ERR_* there). */
+int cyto_csv_format_fields(const void *values, int dtype, int64_t n, char *out, int64_t cap, int32_t *lens);
+
 /* ---- a MatrixMarket coordinate file read dense (cytospace_amd.common.read_mtx_device): what scipy.io.mmread(path).toarray() holds,
  * parsed and scattered on the device.  The caller parses the banner, the comments and the size line "G C nnz"; the
  * nnz entry lines "row col value" start at byte data_offset.  field: 0 integer (out: int64 values, duplicate entries summed with

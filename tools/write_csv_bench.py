@@ -1,0 +1,152 @@
+"""write_csv_device (the device CSV writer, csrc/csv.hip) against the host path of save_results for new_scRNA.csv (DataFrame.loc on the
+generated columns, DataFrame.to_csv) on the same frame in the same process.
+
+  python tools/write_csv_bench.py [--genes 5000] [--cells 8000] [--selected 4000] [--reps 3] [--host-reps 3]
+                                  [--big-genes 20000 --big-cells 40000 --big-selected 30000] [--block-bytes 0] [--out DIR]
+
+Input: genes x cells Poisson counts held as float64 (what the place-holder sampler leaves: integer-valued reals), labelled GENE_* /
+CELL_*; the last `selected` cells are the generated ones, as in a place-holder run.  Timed with a host clock around the whole call
+(the device call ends after its last write()), into a temporary directory, after a small warm-up call of each path; the two paths'
+calls alternate.  Legs: both paths at genes x cells (min / median / max, the files compared byte for byte, the device's phase split
+as the median over its calls, and the text bytes per second of kernels_s), and the device alone at the big shape (skipped when 0).
+One JSON line per leg; with --out they are appended to DIR/write_csv_bench.jsonl."""
+import argparse
+import json
+import os
+import shutil
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+PHASES = ("labels_s", "library_s", "upload_s", "kernels_s", "download_s", "write_s", "total_s")
+
+
+def make_frame(G, N, seed):
+    import pandas as pd
+    rng = np.random.default_rng(seed)
+    x = np.empty((G, N), np.float64)
+    for g0 in range(0, G, 1000):
+        x[g0:g0 + 1000] = rng.poisson(1.5, (min(1000, G - g0), N))
+    return pd.DataFrame(x, index=[f"GENE_{i}" for i in range(G)], columns=[f"CELL_{i}" for i in range(N)], copy=False)
+
+
+def strip(names):
+    return [str(n)[5:] for n in names]
+
+
+def host_path(path, frame, known):
+    """What save_results does for new_scRNA.csv without a device."""
+    t = time.perf_counter()
+    generated = frame.loc[:, ~frame.columns.isin(known)]
+    generated.index = strip(generated.index.astype(str))
+    generated.columns = strip(generated.columns.astype(str))
+    t1 = time.perf_counter()
+    generated.to_csv(path)
+    t2 = time.perf_counter()
+    return {"gather_s": t1 - t, "to_csv_s": t2 - t1, "total_s": t2 - t}
+
+
+def device_path(path, frame, known, block_bytes):
+    from cytospace_amd.post_processing import write_csv_device
+    t = time.perf_counter()
+    positions = np.flatnonzero(~frame.columns.isin(known))
+    info = write_csv_device(path, frame, positions, index_labels=strip(frame.index.astype(str)),
+                            column_labels=strip(frame.columns[positions].astype(str)), block_bytes=block_bytes, return_info=True)
+    info["call_s"] = time.perf_counter() - t                 # isin and the label stripping included, as save_results pays them
+    assert info["path"] == "device", info
+    return info
+
+
+def spread(ts):
+    return {"min": round(min(ts), 4), "median": round(float(np.median(ts)), 4), "max": round(max(ts), 4), "n": len(ts)}
+
+
+def medians(infos, keys):
+    return {k: round(float(np.median([i[k] for i in infos])), 4) for k in keys}
+
+
+def digest(path):
+    import hashlib
+    h = hashlib.sha256()
+    with open(path, "rb") as f:
+        while True:
+            b = f.read(64 << 20)
+            if not b:
+                return h.hexdigest()
+            h.update(b)
+
+
+def leg(G, N, C, reps, host_reps, block_bytes, d, seed):
+    frame = make_frame(G, N, seed)
+    known = frame.columns[:N - C]
+    pd_, ph_ = os.path.join(d, "device.csv"), os.path.join(d, "host.csv")
+    dev, host = [], []
+    for r in range(max(reps, host_reps)):                    # alternate the two paths
+        if r < reps:
+            dev.append(device_path(pd_, frame, known, block_bytes))
+        if r < host_reps:
+            host.append(host_path(ph_, frame, known))
+    out = {"genes": G, "cells": N, "selected": C, "dtype": "float64", "fields": G * C, "bytes": dev[0]["bytes"], "blocks": dev[0]["blocks"],
+           "device_s": spread([i["call_s"] for i in dev]), "device_phases": medians(dev, PHASES)}
+    k = out["device_phases"]["kernels_s"]
+    out["text_bytes_per_kernel_second"] = round(dev[0]["bytes"] / k) if k > 0 else None
+    if host:
+        out["host_s"] = spread([i["total_s"] for i in host])
+        out["host_phases"] = medians(host, ("gather_s", "to_csv_s"))
+        out["speedup_median"] = round(out["host_s"]["median"] / out["device_s"]["median"], 2)
+        out["equal"] = digest(pd_) == digest(ph_)
+        assert out["equal"], "the device's file differs from the host's"
+    for p in (pd_, ph_):
+        if os.path.exists(p):
+            os.remove(p)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--genes", type=int, default=5000)
+    ap.add_argument("--cells", type=int, default=8000)
+    ap.add_argument("--selected", type=int, default=4000)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--host-reps", type=int, default=3)
+    ap.add_argument("--big-genes", type=int, default=0)
+    ap.add_argument("--big-cells", type=int, default=0)
+    ap.add_argument("--big-selected", type=int, default=0)
+    ap.add_argument("--big-reps", type=int, default=1)
+    ap.add_argument("--block-bytes", type=int, default=0)
+    ap.add_argument("--tmp", default=None, help="directory for the files written (default: the system's temporary directory)")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import ctypes
+    from cytospace_amd import _lib
+    name = ctypes.create_string_buffer(256)
+    _lib.check(_lib.lib().cyto_device_name(0, name, 256))
+    d = tempfile.mkdtemp(prefix="write_csv_bench_", dir=a.tmp)
+    lines = []
+    try:
+        warm = leg(60, 300, 200, 1, 1, 0, d, 7)              # warm-up: library, HIP, kernels, pandas' writer
+        assert warm["equal"]
+        legs = []
+        if a.genes and a.cells:
+            legs.append((a.genes, a.cells, a.selected or a.cells, a.reps, a.host_reps, 0))
+        if a.big_genes and a.big_cells:
+            legs.append((a.big_genes, a.big_cells, a.big_selected or a.big_cells, a.big_reps, 0, 1))
+        for G, N, C, reps, host_reps, seed in legs:
+            res = dict(device=name.value.decode(), **leg(G, N, C, reps, host_reps, a.block_bytes, d, seed))
+            lines.append(json.dumps(res))
+            print(lines[-1], flush=True)
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "write_csv_bench.jsonl"), "a") as f:
+            f.write("".join(l + "\n" for l in lines))
+
+
+if __name__ == "__main__":
+    main()
