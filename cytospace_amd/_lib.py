@@ -23,6 +23,8 @@ CYTO_DTYPE_F32, CYTO_DTYPE_F64, CYTO_DTYPE_U16, CYTO_DTYPE_U8, CYTO_DTYPE_I32, C
 CYTO_MTX_ERR_FRACTION, CYTO_MTX_ERR_NONFINITE, CYTO_MTX_ERR_MAGNITUDE, CYTO_MTX_ERR_SQUARE, CYTO_MTX_ERR_IO = range(2, 7)
 # cyto_csv_info.reason with CYTO_ERR_UNSUPPORTED (include/cytohip.h: CYTO_CSV_ERR_*)
 CYTO_CSV_ERR_FRACTION, CYTO_CSV_ERR_NONFINITE, CYTO_CSV_ERR_MAGNITUDE, CYTO_CSV_ERR_IO = 2, 3, 4, 6
+# flags of cyto_mtx_write_ex / cyto_csv_write_ex and their host hooks (include/cytohip.h)
+CYTO_TEXT_FRACTIONS = 1
 
 
 class CytoHipError(RuntimeError):
@@ -215,6 +217,19 @@ def lib():
         L.cyto_csv_write.restype = ctypes.c_int
         L.cyto_csv_format_fields.argtypes = [vp, i32, i64, vp, i64, vp]
         L.cyto_csv_format_fields.restype = ctypes.c_int
+        L.cyto_mtx_write_ex.argtypes = [ctypes.c_char_p, i64, i64, vp, i64, i32, vp, i64, i64, i32, i32, ctypes.POINTER(MtxInfo)]
+        L.cyto_mtx_write_ex.restype = ctypes.c_int
+        L.cyto_mtx_format_entries_ex.argtypes = [vp, vp, vp, i32, i64, vp, vp, i32]
+        L.cyto_mtx_format_entries_ex.restype = ctypes.c_int
+        L.cyto_csv_write_ex.argtypes = [ctypes.c_char_p, i64, i64, vp, i64, i32, vp, i64, vp, i64, vp, vp, i64, i32, i32,
+                                        ctypes.POINTER(CsvInfo)]
+        L.cyto_csv_write_ex.restype = ctypes.c_int
+        L.cyto_csv_format_fields_ex.argtypes = [vp, i32, i64, vp, i64, vp, i32]
+        L.cyto_csv_format_fields_ex.restype = ctypes.c_int
+        L.cyto_shortest_digits.argtypes = [vp, i32, i64, vp, vp]
+        L.cyto_shortest_digits.restype = ctypes.c_int
+        L.cyto_text_pow10.argtypes = [i32, vp]
+        L.cyto_text_pow10.restype = ctypes.c_int
         L.cyto_mtx_read.argtypes = [ctypes.c_char_p, i64, i64, i64, i64, i32, vp, i64, i32, ctypes.POINTER(MtxReadInfo)]
         L.cyto_mtx_read.restype = ctypes.c_int
         L.cyto_mtx_parse_entries.argtypes = [vp, i64, vp, i32, i64, i64, vp, vp, vp, vp, vp]

@@ -5,9 +5,10 @@
 // X is the G x N source matrix, cols the C source columns of the generated cells.  The file is the caller's header line, then per gene
 // the caller's label bytes (quoted by the caller, with their trailing ','), the C values X[gene, cols[j]] separated by ',' and a '\n'
 // (DESIGN.md 4.1d').  A gene's cells are cut into segments of 512; a field is the value's text and its terminator (',' or, for the
-// gene's last cell, '\n'), 21 bytes at the most.
+// gene's last cell, '\n'), 21 bytes at the most (25 with CYTO_TEXT_FRACTIONS).
 //   csv_count    (a workgroup per gene and segment) the exact bytes of the segment's fields, plus the label's before segment 0; and
-//                which values are outside the device grammar (a real value that is not an integer below 2^53 -- 2^24 for float32).
+//                which values are outside the device grammar (a real value that is not an integer below 2^53 -- 2^24 for float32; with
+//                CYTO_TEXT_FRACTIONS only a value that is not finite: every other real is written by its shortest digits, shortest.h).
 //   csv_scan     (one workgroup) turns the segments' byte counts into int64 offsets into the slab's text.
 //   csv_format   (a workgroup per gene and segment) computes the field lengths again, scans them, formats the fields into LDS at the
 //                position their bytes have within the 16-byte chunks of the output, and stores whole chunks with 16-byte stores; the
@@ -16,6 +17,8 @@
 // counted, scanned, formatted, downloaded into one of two pinned buffers and written; slab k + 1 runs on the other stream while slab
 // k is written, so device memory is bounded by the slab, not by G.
 // fmt_value is the one formatter: the count pass, the format pass and the host (cyto_csv_format_fields) all call it.
+// FRAC: the instantiations of CYTO_TEXT_FRACTIONS (real types only); without it everything is as it was before the flag existed.
+#include "shortest.h"
 #include "text_write.h"
 
 #include <fcntl.h>
@@ -31,50 +34,127 @@ using namespace cyto;
 constexpr int WG = 256;
 constexpr int EPT = 2;                                   // consecutive cells per thread
 constexpr int SEG = WG * EPT;                            // cells per segment
-constexpr int MAX_FIELD = 21;                            // "-9223372036854775808" and its terminator
-constexpr int STAGE = SEG * MAX_FIELD + 16;              // a segment's fields, shifted by up to 15 bytes
+template <bool FRAC> struct Lim {
+    static constexpr int MAX_FIELD = FRAC ? 25 : 21;     // "-9223372036854775808" and its terminator; FRAC: "-1.7976931348623157e+308"
+    static constexpr int STAGE = SEG * MAX_FIELD + 16;   // a segment's fields, shifted by up to 15 bytes
+};
 constexpr int64_t DEFAULT_BLOCK = int64_t(32) << 20;
 constexpr int64_t MAX_BLOCK = int64_t(1) << 40;
 
 // A value as the formatter takes it.  status: 0 inside the grammar, else CYTO_CSV_ERR_* (neg and mag are then those of a zero, so
 // that both passes give the value the same, short field).
+// The value is mag * 10^e10; form: 0 positional, 1 scientific, 2 by the exponent, as repr(float) has it (e10 and form: FRAC only).
 struct Val {
     int status;
     bool neg;
     uint64_t mag;
+    int e10, form;
 };
 
 template <typename T> __host__ __device__ inline Val classify_int(T v) {
     const bool neg = v < 0;
-    return Val{0, neg, neg ? (uint64_t)0 - (uint64_t)(int64_t)v : (uint64_t)v};
+    return Val{0, neg, neg ? (uint64_t)0 - (uint64_t)(int64_t)v : (uint64_t)v, 0, 0};
 }
 // pandas writes repr(float(v)): for an integer below 2^53 (a float32 is widened first: below 2^24, where the device keeps the
 // window the MatrixMarket writer has) the integer's digits and ".0"; a zero keeps its sign.
-__host__ __device__ inline Val classify_real(double v, double limit) {
-    const double a = fabs(v);
-    if (!(a <= 1.7976931348623157e308)) return Val{CYTO_CSV_ERR_NONFINITE, false, 0};
-    if (a >= limit) return Val{CYTO_CSV_ERR_MAGNITUDE, false, 0};
-    if (a != floor(a)) return Val{CYTO_CSV_ERR_FRACTION, false, 0};
-    return Val{0, __builtin_signbit(v) != 0, (uint64_t)a};
+// FRAC: an integer inside the window keeps the path it has without the flag; every other finite value gets its shortest digits.
+// numpy writes a float32 in the scientific form when |v| < 1e-4 or |v| >= 1e16, by the value: float32(1e-4) = 0x38d1b717 lies below
+// 1e-4 (its digits, 1e-04, would be positional by their exponent), and the first float32 that is no less than 1e16 is 0x5a0e1bca.
+__host__ __device__ inline Val shortest(float v) {
+    const uint32_t b = __builtin_bit_cast(uint32_t, v) & 0x7fffffffu;
+    const Decimal d = shortest_digits32(b);
+    return Val{0, false, d.digits, d.exp10, b <= 0x38d1b717u || b >= 0x5a0e1bcau ? 1 : 0};
 }
-__host__ __device__ inline Val classify(uint8_t v) { return classify_int(v); }
-__host__ __device__ inline Val classify(uint16_t v) { return classify_int(v); }
-__host__ __device__ inline Val classify(int32_t v) { return classify_int(v); }
-__host__ __device__ inline Val classify(int64_t v) { return classify_int(v); }
-__host__ __device__ inline Val classify(float v) { return classify_real((double)v, 16777216.0); }
-__host__ __device__ inline Val classify(double v) { return classify_real(v, 9007199254740992.0); }
+__host__ __device__ inline Val shortest(double v) {
+    const Decimal d = shortest_digits64(__builtin_bit_cast(uint64_t, v));
+    return Val{0, false, d.digits, d.exp10, 2};
+}
+template <bool FRAC, typename T> __host__ __device__ inline Val classify_real(T t, double limit) {
+    const double v = (double)t;
+    const double a = fabs(v);
+    if (!(a <= 1.7976931348623157e308)) return Val{CYTO_CSV_ERR_NONFINITE, false, 0, 0, 0};
+    if (FRAC) {
+        if (a < limit && a == floor(a)) return Val{0, __builtin_signbit(v) != 0, (uint64_t)a, 0, 0};
+        Val r = shortest(t);
+        r.neg = v < 0.0;
+        return r;
+    }
+    if (a >= limit) return Val{CYTO_CSV_ERR_MAGNITUDE, false, 0, 0, 0};
+    if (a != floor(a)) return Val{CYTO_CSV_ERR_FRACTION, false, 0, 0, 0};
+    return Val{0, __builtin_signbit(v) != 0, (uint64_t)a, 0, 0};
+}
+template <bool FRAC> __host__ __device__ inline Val classify(uint8_t v) { return classify_int(v); }
+template <bool FRAC> __host__ __device__ inline Val classify(uint16_t v) { return classify_int(v); }
+template <bool FRAC> __host__ __device__ inline Val classify(int32_t v) { return classify_int(v); }
+template <bool FRAC> __host__ __device__ inline Val classify(int64_t v) { return classify_int(v); }
+template <bool FRAC> __host__ __device__ inline Val classify(float v) { return classify_real<FRAC>(v, 16777216.0); }
+template <bool FRAC> __host__ __device__ inline Val classify(double v) { return classify_real<FRAC>(v, 9007199254740992.0); }
 template <typename T> struct is_real { static constexpr bool value = false; };
 template <> struct is_real<float> { static constexpr bool value = true; };
 template <> struct is_real<double> { static constexpr bool value = true; };
 
 // The value's text, without a terminator; returns its length.  WRITE = false: the length alone (o is not touched).
-template <bool WRITE> __host__ __device__ inline int fmt_value(uint8_t *o, bool real, bool neg, uint64_t m) {
+// FRAC, a value with e10 != 0 or form != 0 (d1 ... dnd: the digits of m, e = e10 + nd - 1 the decimal exponent of d1):
+//   positional   e10 >= 0: the digits, e10 zeros, ".0"; e >= 0: a '.' after digit e + 1; e < 0: "0.", -e - 1 zeros, the digits.
+//   scientific   d1[.d2 ... dnd]e[+-]XX, at least two exponent digits.
+template <bool WRITE, bool FRAC> __host__ __device__ inline int fmt_value(uint8_t *o, bool real, const Val &val) {
+    const bool neg = val.neg;
+    const uint64_t m = val.mag;
     int n = 0;
     if (neg) {
         if (WRITE) o[n] = '-';
         n++;
     }
     const int nd = ndigits64(m);
+    if (FRAC && (val.e10 != 0 || val.form != 0)) {
+        const int e10 = val.e10;
+        int e = e10 + nd - 1;
+        if (val.form == 1 || (val.form == 2 && (e < -4 || e >= 16))) {
+            if (WRITE) {
+                put_digits(o + n + 1, m, nd);
+                o[n] = o[n + 1];
+                o[n + 1] = '.';
+            }
+            n += nd == 1 ? 1 : nd + 1;                  // (a lone digit: the '.' is overwritten)
+            if (WRITE) {
+                o[n] = 'e';
+                o[n + 1] = e < 0 ? '-' : '+';
+            }
+            n += 2;
+            if (e < 0) e = -e;
+            const int ne = e < 100 ? 2 : 3;
+            if (WRITE) {
+                if (ne == 3) o[n] = (uint8_t)('0' + e / 100);
+                o[n + ne - 2] = (uint8_t)('0' + e / 10 % 10);
+                o[n + ne - 1] = (uint8_t)('0' + e % 10);
+            }
+            return n + ne;
+        }
+        if (e10 >= 0) {
+            if (WRITE) {
+                put_digits(o + n, m, nd);
+                for (int i = 0; i < e10; i++) o[n + nd + i] = '0';
+                o[n + nd + e10] = '.';
+                o[n + nd + e10 + 1] = '0';
+            }
+            return n + nd + e10 + 2;
+        }
+        if (e >= 0) {
+            if (WRITE) {
+                put_digits(o + n + 1, m, nd);
+                for (int i = 0; i <= e; i++) o[n + i] = o[n + i + 1];
+                o[n + e + 1] = '.';
+            }
+            return n + nd + 1;
+        }
+        if (WRITE) {
+            o[n] = '0';
+            o[n + 1] = '.';
+            for (int i = 0; i < -e - 1; i++) o[n + 2 + i] = '0';
+            put_digits(o + n + 1 - e, m, nd);
+        }
+        return n + 1 - e + nd;
+    }
     if (WRITE) put_digits(o + n, m, nd);
     n += nd;
     if (real) {
@@ -88,21 +168,21 @@ template <bool WRITE> __host__ __device__ inline int fmt_value(uint8_t *o, bool 
 }
 
 // The longest field (text and terminator) a value of the type can have: what a slab's text is bounded by before it is counted.
-int max_field(int dt) {
+int max_field(int dt, bool frac) {
     switch (dt) {
     case CYTO_DTYPE_U8: return 4;                        // "255,"
     case CYTO_DTYPE_U16: return 6;                       // "65535,"
     case CYTO_DTYPE_I32: return 12;                      // "-2147483648,"
-    case CYTO_DTYPE_F32: return 12;                      // "-16777215.0,"
-    case CYTO_DTYPE_F64: return 20;                      // "-9007199254740991.0,"
+    case CYTO_DTYPE_F32: return frac ? 20 : 12;          // "-16777215.0,"; "-9999999000000000.0,"
+    case CYTO_DTYPE_F64: return frac ? 25 : 20;          // "-9007199254740991.0,"; "-1.7976931348623157e+308,"
     }
-    return MAX_FIELD;
+    return Lim<false>::MAX_FIELD;
 }
 
 // Workgroup w of the launch: the slab's gene r = w / nseg, segment s = w % nseg.  X: the slab's rows; label_off[r .. r + 1]: gene r's
 // label within the file's label bytes.  seg_bytes[w] := the bytes of the segment's fields, with the label's for s = 0;
 // *flags |= 1 << CYTO_CSV_ERR_* for every kind of value outside the grammar.
-template <typename T>
+template <typename T, bool FRAC>
 __global__ __launch_bounds__(WG) void csv_count(const T *X, int64_t ldx, const int64_t *cols, int64_t C, int nseg, const int64_t *label_off,
                                                 int64_t *seg_bytes, int *flags) {
     const int64_t r = blockIdx.x / nseg;
@@ -113,9 +193,9 @@ __global__ __launch_bounds__(WG) void csv_count(const T *X, int64_t ldx, const i
     for (int k = 0; k < EPT; k++) {
         const int64_t j = (int64_t)s * SEG + threadIdx.x * EPT + k;
         if (j >= C) break;
-        const Val v = classify(xr[cols[j]]);
+        const Val v = classify<FRAC>(xr[cols[j]]);
         if (v.status) bad |= 1 << v.status;
-        mine += fmt_value<false>(nullptr, is_real<T>::value, v.neg, v.mag) + 1;
+        mine += fmt_value<false, FRAC>(nullptr, is_real<T>::value, v) + 1;
     }
     int tot;
     wg_scan<WG>(mine, &tot);
@@ -141,10 +221,10 @@ __global__ __launch_bounds__(WG) void csv_scan(const int64_t *seg_bytes, int64_t
 
 // Workgroup w as in csv_count.  labels: the slab's label bytes, gene r's at label_off[r] - label_off[0]; out: the slab's text (16-byte
 // aligned).
-template <typename T>
+template <typename T, bool FRAC>
 __global__ __launch_bounds__(WG) void csv_format(const T *X, int64_t ldx, const int64_t *cols, int64_t C, int nseg, const int64_t *label_off,
                                                  const uint8_t *labels, const int64_t *seg_off, uint8_t *out) {
-    __shared__ uint4 stage4[(STAGE + 15) / 16];
+    __shared__ uint4 stage4[(Lim<FRAC>::STAGE + 15) / 16];
     uint8_t *stage = reinterpret_cast<uint8_t *>(stage4);
     const int64_t r = blockIdx.x / nseg;
     const int s = (int)(blockIdx.x % nseg);
@@ -156,8 +236,8 @@ __global__ __launch_bounds__(WG) void csv_format(const T *X, int64_t ldx, const 
         const int64_t j = (int64_t)s * SEG + threadIdx.x * EPT + k;
         len[k] = 0;
         if (j < C) {
-            v[k] = classify(xr[cols[j]]);
-            len[k] = fmt_value<false>(nullptr, is_real<T>::value, v[k].neg, v[k].mag) + 1;
+            v[k] = classify<FRAC>(xr[cols[j]]);
+            len[k] = fmt_value<false, FRAC>(nullptr, is_real<T>::value, v[k]) + 1;
         }
         mine += len[k];
     }
@@ -176,7 +256,7 @@ __global__ __launch_bounds__(WG) void csv_format(const T *X, int64_t ldx, const 
     for (int k = 0; k < EPT; k++)
         if (len[k]) {
             const int64_t j = (int64_t)s * SEG + threadIdx.x * EPT + k;
-            fmt_value<true>(p, is_real<T>::value, v[k].neg, v[k].mag);
+            fmt_value<true, FRAC>(p, is_real<T>::value, v[k]);
             p[len[k] - 1] = j == C - 1 ? '\n' : ',';
             p += len[k];
         }
@@ -193,15 +273,22 @@ __global__ __launch_bounds__(WG) void csv_format(const T *X, int64_t ldx, const 
     }
 }
 
-// CALL with T bound to the element type of CYTO_DTYPE_* dt
-#define CSV_DISPATCH(dt, CALL)                                     \
-    switch (dt) {                                                  \
-    case CYTO_DTYPE_F32: { using T = float; CALL; } break;         \
-    case CYTO_DTYPE_F64: { using T = double; CALL; } break;        \
-    case CYTO_DTYPE_U16: { using T = uint16_t; CALL; } break;      \
-    case CYTO_DTYPE_U8: { using T = uint8_t; CALL; } break;        \
-    case CYTO_DTYPE_I32: { using T = int32_t; CALL; } break;       \
-    default: { using T = int64_t; CALL; } break;                   \
+// The statement(s) after frac, with T bound to the element type of CYTO_DTYPE_* dt and FRAC to frac (false for the integer types, whose
+// text has one form)
+#define CSV_DISPATCH(dt, frac, ...)                                                               \
+    switch (dt) {                                                                                 \
+    case CYTO_DTYPE_F32:                                                                          \
+        if (frac) { using T = float; constexpr bool FRAC = true; __VA_ARGS__; }                   \
+        else { using T = float; constexpr bool FRAC = false; __VA_ARGS__; }                       \
+        break;                                                                                    \
+    case CYTO_DTYPE_F64:                                                                          \
+        if (frac) { using T = double; constexpr bool FRAC = true; __VA_ARGS__; }                  \
+        else { using T = double; constexpr bool FRAC = false; __VA_ARGS__; }                      \
+        break;                                                                                    \
+    case CYTO_DTYPE_U16: { using T = uint16_t; constexpr bool FRAC = false; __VA_ARGS__; } break; \
+    case CYTO_DTYPE_U8: { using T = uint8_t; constexpr bool FRAC = false; __VA_ARGS__; } break;   \
+    case CYTO_DTYPE_I32: { using T = int32_t; constexpr bool FRAC = false; __VA_ARGS__; } break;  \
+    default: { using T = int64_t; constexpr bool FRAC = false; __VA_ARGS__; } break;              \
     }
 
 }  // namespace
@@ -209,7 +296,15 @@ __global__ __launch_bounds__(WG) void csv_format(const T *X, int64_t ldx, const 
 int cyto_csv_write(const char *path, int64_t G, int64_t N, const void *x, int64_t ldx, int x_dtype, const int64_t *cols, int64_t C,
                    const char *header, int64_t header_len, const char *labels, const int64_t *label_off, int64_t block_bytes,
                    int device_id, cyto_csv_info *info) {
+    return cyto_csv_write_ex(path, G, N, x, ldx, x_dtype, cols, C, header, header_len, labels, label_off, block_bytes, device_id, 0, info);
+}
+
+int cyto_csv_write_ex(const char *path, int64_t G, int64_t N, const void *x, int64_t ldx, int x_dtype, const int64_t *cols, int64_t C,
+                      const char *header, int64_t header_len, const char *labels, const int64_t *label_off, int64_t block_bytes,
+                      int device_id, int flags, cyto_csv_info *info) {
     const size_t es = dtype_size(x_dtype);
+    const bool frac = (flags & CYTO_TEXT_FRACTIONS) != 0;
+    if (flags & ~CYTO_TEXT_FRACTIONS) return CYTO_ERR_BAD_ARG;
     if (!path || !x || !cols || !header || !labels || !label_off || !info || es == 0 || G <= 0 || N <= 0 || C <= 0 || ldx < N ||
         header_len < 0 || block_bytes < 0 || G > 0x7fffffffll || C > 0x7fffffffll)
         return CYTO_ERR_BAD_ARG;
@@ -231,7 +326,7 @@ int cyto_csv_write(const char *path, int64_t G, int64_t N, const void *x, int64_
     // rows are capped too (N may be far above C), and so are the workgroups of one launch.
     const int nseg = (int)((C + SEG - 1) / SEG);
     const int64_t cap = std::min(block_bytes ? block_bytes : DEFAULT_BLOCK, MAX_BLOCK);
-    const int64_t in_cap = 4 * cap, row_in = ldx * (int64_t)es, row_text = C * max_field(x_dtype);
+    const int64_t in_cap = 4 * cap, row_in = ldx * (int64_t)es, row_text = C * max_field(x_dtype, frac);
     const int64_t max_rows = std::max<int64_t>(1, (int64_t(1) << 30) / nseg);
     std::vector<int64_t> first;                         // slab k: genes [first[k], first[k + 1])
     int64_t most_text = 0, most_rows = 0, most_labels = 0;
@@ -289,12 +384,12 @@ int cyto_csv_write(const char *path, int64_t G, int64_t N, const void *x, int64_
         if (nlab > 0) CYTO_HIP(hipMemcpyAsync(dlab[b].p, labels + label_off[g0], (size_t)nlab, hipMemcpyHostToDevice, s));
         CYTO_HIP(hipMemsetAsync(scal[b].p, 0, 16, s));
         CYTO_HIP(hipEventRecord(ev[5 * b + 1], s));
-        CSV_DISPATCH(x_dtype, hipLaunchKernelGGL(csv_count<T>, dim3(grid), dim3(WG), 0, s, dx[b].as<T>(), ldx, dcols.as<int64_t>(), C, nseg,
+        CSV_DISPATCH(x_dtype, frac, hipLaunchKernelGGL((csv_count<T, FRAC>), dim3(grid), dim3(WG), 0, s, dx[b].as<T>(), ldx, dcols.as<int64_t>(), C, nseg,
                                                  dlaboff[b].as<int64_t>(), dseg[b].as<int64_t>(), scal[b].as<int>() + 2));
         CYTO_HIP(hipGetLastError());
         hipLaunchKernelGGL(csv_scan, dim3(1), dim3(WG), 0, s, dseg[b].as<int64_t>(), R * nseg, doff[b].as<int64_t>(), scal[b].as<int64_t>());
         CYTO_HIP(hipGetLastError());
-        CSV_DISPATCH(x_dtype, hipLaunchKernelGGL(csv_format<T>, dim3(grid), dim3(WG), 0, s, dx[b].as<T>(), ldx, dcols.as<int64_t>(), C, nseg,
+        CSV_DISPATCH(x_dtype, frac, hipLaunchKernelGGL((csv_format<T, FRAC>), dim3(grid), dim3(WG), 0, s, dx[b].as<T>(), ldx, dcols.as<int64_t>(), C, nseg,
                                                  dlaboff[b].as<int64_t>(), dlab[b].as<uint8_t>(), doff[b].as<int64_t>(),
                                                  dbuf[b].as<uint8_t>()));
         CYTO_HIP(hipGetLastError());
@@ -306,9 +401,9 @@ int cyto_csv_write(const char *path, int64_t G, int64_t N, const void *x, int64_
     auto settle = [&](int64_t k) -> int {
         const int b = (int)(k & 1);
         CYTO_HIP(hipStreamSynchronize(st[b].s));
-        const int flags = (int)(hs[b][1] & 0xffffffff);
+        const int bad = (int)(hs[b][1] & 0xffffffff);
         for (int kind : {CYTO_CSV_ERR_NONFINITE, CYTO_CSV_ERR_FRACTION, CYTO_CSV_ERR_MAGNITUDE})
-            if (flags & (1 << kind)) return refuse(kind);
+            if (bad & (1 << kind)) return refuse(kind);
         len[b] = hs[b][0];
         if (len[b] <= 0 || len[b] > most_text) return CYTO_ERR_INTERNAL;
         CYTO_HIP(hipEventRecord(ev[5 * b + 3], st[b].s));
@@ -344,18 +439,26 @@ int cyto_csv_write(const char *path, int64_t G, int64_t N, const void *x, int64_
 }
 
 int cyto_csv_format_fields(const void *values, int dtype, int64_t n, char *out, int64_t cap, int32_t *lens) {
-    if (n < 0 || dtype_size(dtype) == 0 || cap < 20 * n || (n > 0 && (!values || !out || !lens))) return CYTO_ERR_BAD_ARG;
+    return cyto_csv_format_fields_ex(values, dtype, n, out, cap, lens, 0);
+}
+
+int cyto_csv_format_fields_ex(const void *values, int dtype, int64_t n, char *out, int64_t cap, int32_t *lens, int flags) {
+    const bool frac = (flags & CYTO_TEXT_FRACTIONS) != 0;
+    if ((flags & ~CYTO_TEXT_FRACTIONS) || n < 0 || dtype_size(dtype) == 0 || cap < (frac ? 24 : 20) * n || (n > 0 && (!values || !out || !lens)))
+        return CYTO_ERR_BAD_ARG;
     uint8_t *o = reinterpret_cast<uint8_t *>(out);
     int64_t at = 0;
     for (int64_t i = 0; i < n; i++) {
-        Val v{};
-        bool real = false;
-        CSV_DISPATCH(dtype, (v = classify(static_cast<const T *>(values)[i]), real = is_real<T>::value));
-        if (v.status) {
-            lens[i] = -v.status;
+        int status = 0;
+        CSV_DISPATCH(dtype, frac, {
+            const Val v = classify<FRAC>(static_cast<const T *>(values)[i]);
+            status = v.status;
+            if (!status) lens[i] = fmt_value<true, FRAC>(o + at, is_real<T>::value, v);
+        });
+        if (status) {
+            lens[i] = -status;
             return CYTO_ERR_UNSUPPORTED;
         }
-        lens[i] = fmt_value<true>(o + at, real, v.neg, v.mag);
         at += lens[i];
     }
     return CYTO_OK;

@@ -5,7 +5,8 @@
 // "<gene+1> <cell+1> <value>\n" per non-zero X[gene, cols[cell]], genes ascending, then cells ascending.
 //   mtx_count    (a workgroup per gene) walks the gene's cells a segment of 512 at a time: the non-zeros and the exact bytes of their
 //                lines per segment, the segment's offset within the gene's text, the gene's totals; and which values are outside the
-//                device grammar (a real value that is not an integer below 2^53 -- 2^24 for float32).
+//                device grammar (a real value that is not an integer below 2^53 -- 2^24 for float32; with CYTO_TEXT_FRACTIONS only a
+//                value that is not finite: every other real is written by its shortest digits, shortest.h).
 //   mtx_scan     (one workgroup) turns the genes' byte counts into int64 offsets into the body, and sums the non-zeros.
 //   mtx_format   (a workgroup per gene and segment) computes the line lengths again, scans them, formats the lines into LDS at the
 //                position their bytes have within the 16-byte chunks of the output, and stores whole chunks with 16-byte stores;
@@ -13,6 +14,8 @@
 // The body is formatted in blocks of whole genes that fit a bounded device buffer; block k is downloaded into one of two pinned
 // buffers while block k + 1 is formatted and block k - 1 is written to the file.
 // fmt_line is the one formatter: the count pass, the format pass and the host (cyto_mtx_format_entries) all call it.
+// FRAC: the instantiations of CYTO_TEXT_FRACTIONS (real types only); without it everything is as it was before the flag existed.
+#include "shortest.h"
 #include "text_write.h"
 
 #include <fcntl.h>
@@ -28,47 +31,60 @@ using namespace cyto;
 constexpr int WG = 256;
 constexpr int EPT = 2;                                   // consecutive cells per thread
 constexpr int SEG = WG * EPT;                            // cells per segment
-constexpr int MAX_VALUE = 21;                            // "-9.007199254740991E15"; an int64 takes at most 20
-constexpr int MAX_LINE = 10 + 1 + 10 + 1 + MAX_VALUE + 1;   // G and C are below 2^31: at most 10 digits each
-constexpr int STAGE = SEG * MAX_LINE + 16;               // a segment's text, shifted by up to 15 bytes
+template <bool FRAC> struct Lim {
+    static constexpr int MAX_VALUE = FRAC ? 24 : 21;     // "-9.007199254740991E15", an int64 takes at most 20; FRAC: "-1.7976931348623157E-308"
+    static constexpr int MAX_LINE = 10 + 1 + 10 + 1 + MAX_VALUE + 1;   // G and C are below 2^31: at most 10 digits each
+    static constexpr int STAGE = SEG * MAX_LINE + 16;    // a segment's text, shifted by up to 15 bytes
+};
 constexpr int64_t DEFAULT_BLOCK = int64_t(32) << 20;
 
 // A value as the formatter takes it.  status: 0 a non-zero inside the grammar, 1 a zero (not written), else CYTO_MTX_ERR_*.
+// The value is mag * 10^e10 (e10 != 0 only with FRAC).
 struct Val {
     int status;
     bool neg;
     uint64_t mag;
+    int e10;
 };
 
 template <typename T> __host__ __device__ inline Val classify_int(T v) {
     const bool neg = v < 0;
     const uint64_t m = neg ? (uint64_t)0 - (uint64_t)(int64_t)v : (uint64_t)v;
-    return Val{m == 0 ? 1 : 0, neg, m};
+    return Val{m == 0 ? 1 : 0, neg, m, 0};
 }
-__host__ __device__ inline Val classify_real(double v, double limit) {
-    if (v == 0.0) return Val{1, false, 0};
-    const double a = fabs(v);
-    if (!(a <= 1.7976931348623157e308)) return Val{CYTO_MTX_ERR_NONFINITE, false, 0};
-    if (a >= limit) return Val{CYTO_MTX_ERR_MAGNITUDE, false, 0};
-    if (a != floor(a)) return Val{CYTO_MTX_ERR_FRACTION, false, 0};
-    return Val{0, v < 0.0, (uint64_t)a};
+__host__ __device__ inline Decimal shortest(float v) { return shortest_digits32(__builtin_bit_cast(uint32_t, v)); }
+__host__ __device__ inline Decimal shortest(double v) { return shortest_digits64(__builtin_bit_cast(uint64_t, v)); }
+// FRAC: an integer inside the window keeps the path it has without the flag; every other finite value gets its shortest digits.
+template <bool FRAC, typename T> __host__ __device__ inline Val classify_real(T v, double limit) {
+    const double w = (double)v;
+    if (w == 0.0) return Val{1, false, 0, 0};
+    const double a = fabs(w);
+    if (!(a <= 1.7976931348623157e308)) return Val{CYTO_MTX_ERR_NONFINITE, false, 0, 0};
+    if (FRAC) {
+        if (a < limit && a == floor(a)) return Val{0, w < 0.0, (uint64_t)a, 0};
+        const Decimal d = shortest(v);
+        return Val{0, w < 0.0, d.digits, d.exp10};
+    }
+    if (a >= limit) return Val{CYTO_MTX_ERR_MAGNITUDE, false, 0, 0};
+    if (a != floor(a)) return Val{CYTO_MTX_ERR_FRACTION, false, 0, 0};
+    return Val{0, w < 0.0, (uint64_t)a, 0};
 }
-__host__ __device__ inline Val classify(uint8_t v) { return classify_int(v); }
-__host__ __device__ inline Val classify(uint16_t v) { return classify_int(v); }
-__host__ __device__ inline Val classify(int32_t v) { return classify_int(v); }
-__host__ __device__ inline Val classify(int64_t v) { return classify_int(v); }
+template <bool FRAC> __host__ __device__ inline Val classify(uint8_t v) { return classify_int(v); }
+template <bool FRAC> __host__ __device__ inline Val classify(uint16_t v) { return classify_int(v); }
+template <bool FRAC> __host__ __device__ inline Val classify(int32_t v) { return classify_int(v); }
+template <bool FRAC> __host__ __device__ inline Val classify(int64_t v) { return classify_int(v); }
 // scipy writes the shortest digits that read back as the same value OF THE SOURCE TYPE: they are the integer's own digits while
 // the type's spacing is at most 1, that is below 2^24 for float32 and below 2^53 for float64.
-__host__ __device__ inline Val classify(float v) { return classify_real((double)v, 16777216.0); }
-__host__ __device__ inline Val classify(double v) { return classify_real(v, 9007199254740992.0); }
+template <bool FRAC> __host__ __device__ inline Val classify(float v) { return classify_real<FRAC>(v, 16777216.0); }
+template <bool FRAC> __host__ __device__ inline Val classify(double v) { return classify_real<FRAC>(v, 9007199254740992.0); }
 template <typename T> struct is_real { static constexpr bool value = false; };
 template <> struct is_real<float> { static constexpr bool value = true; };
 template <> struct is_real<double> { static constexpr bool value = true; };
 
 // The value's text; returns its length.  WRITE = false: the length alone (o is not touched).
 // integer field: plain decimal.  real field: the digits of m without trailing zeros, a '.' after the first when more than one is
-// left, and "E<k>", k = the digit count of m minus 1, when k > 0.
-template <bool WRITE> __host__ __device__ inline int fmt_value(uint8_t *o, bool real, bool neg, uint64_t m) {
+// left, and "E<k>", k = the digit count of m minus 1 plus e10 (the decimal exponent of the first digit), when k != 0.
+template <bool WRITE, bool FRAC> __host__ __device__ inline int fmt_value(uint8_t *o, bool real, bool neg, uint64_t m, int e10) {
     int n = 0;
     if (neg) {
         if (WRITE) o[n] = '-';
@@ -98,6 +114,22 @@ template <bool WRITE> __host__ __device__ inline int fmt_value(uint8_t *o, bool 
         }
         n += sig + 1;
     }
+    if (FRAC) {                                         // -324 <= k <= 308: no '+', no padding
+        int k = nd - 1 + e10;
+        if (k != 0) {
+            if (WRITE) o[n] = 'E';
+            n++;
+            if (k < 0) {
+                if (WRITE) o[n] = '-';
+                n++;
+                k = -k;
+            }
+            const int ne = ndigits32((uint32_t)k);
+            if (WRITE) put_digits(o + n, (uint64_t)k, ne);
+            n += ne;
+        }
+        return n;
+    }
     int k = nd - 1;                                      // at most 15
     if (k > 0) {
         if (WRITE) o[n] = 'E';
@@ -114,7 +146,7 @@ template <bool WRITE> __host__ __device__ inline int fmt_value(uint8_t *o, bool 
 }
 
 // "<row1> <col1> <value>\n"; returns its length.
-template <bool WRITE> __host__ __device__ inline int fmt_line(uint8_t *o, uint64_t row1, uint64_t col1, bool real, const Val &v) {
+template <bool WRITE, bool FRAC> __host__ __device__ inline int fmt_line(uint8_t *o, uint64_t row1, uint64_t col1, bool real, const Val &v) {
     const int nr = ndigits64(row1), nc = ndigits64(col1);
     if (WRITE) {
         put_digits(o, row1, nr);
@@ -123,14 +155,14 @@ template <bool WRITE> __host__ __device__ inline int fmt_line(uint8_t *o, uint64
         o[nr + 1 + nc] = ' ';
     }
     int n = nr + nc + 2;
-    n += fmt_value<WRITE>(o + n, real, v.neg, v.mag);
+    n += fmt_value<WRITE, FRAC>(o + n, real, v.neg, v.mag, v.e10);
     if (WRITE) o[n] = '\n';
     return n + 1;
 }
 
 // A workgroup per gene g.  seg_off[g * nseg + s] := the bytes of gene g's lines before segment s; row_bytes[g], row_nnz[g] := its
 // totals; *flags |= 1 << CYTO_MTX_ERR_* for every kind of value outside the grammar.
-template <typename T>
+template <typename T, bool FRAC>
 __global__ __launch_bounds__(WG) void mtx_count(const T *X, int64_t ldx, const int64_t *cols, int64_t C, int nseg, int64_t *seg_off,
                                                 int64_t *row_bytes, int64_t *row_nnz, int *flags) {
     const int64_t g = blockIdx.x;
@@ -143,8 +175,8 @@ __global__ __launch_bounds__(WG) void mtx_count(const T *X, int64_t ldx, const i
         for (int k = 0; k < EPT; k++) {
             const int64_t j = (int64_t)s * SEG + threadIdx.x * EPT + k;
             if (j >= C) break;
-            const Val v = classify(xr[cols[j]]);
-            if (v.status == 0) packed += (1 << 16) + fmt_line<false>(nullptr, (uint64_t)g + 1, (uint64_t)j + 1, is_real<T>::value, v);
+            const Val v = classify<FRAC>(xr[cols[j]]);
+            if (v.status == 0) packed += (1 << 16) + fmt_line<false, FRAC>(nullptr, (uint64_t)g + 1, (uint64_t)j + 1, is_real<T>::value, v);
             else if (v.status > 1) bad |= 1 << v.status;
         }
         int tot;
@@ -180,10 +212,10 @@ __global__ __launch_bounds__(WG) void mtx_scan(const int64_t *row_bytes, const i
 
 // Workgroup w of the launch: gene g0 + w / nseg, segment w % nseg.  out: the block's text, its first byte being byte `base` of the body
 // (out is 16-byte aligned).
-template <typename T>
+template <typename T, bool FRAC>
 __global__ __launch_bounds__(WG) void mtx_format(const T *X, int64_t ldx, const int64_t *cols, int64_t C, int nseg, int64_t g0,
                                                  const int64_t *row_off, const int64_t *seg_off, int64_t base, uint8_t *out) {
-    __shared__ uint4 stage4[(STAGE + 15) / 16];
+    __shared__ uint4 stage4[(Lim<FRAC>::STAGE + 15) / 16];
     uint8_t *stage = reinterpret_cast<uint8_t *>(stage4);
     const int64_t g = g0 + blockIdx.x / nseg;
     const int s = (int)(blockIdx.x % nseg);
@@ -195,8 +227,8 @@ __global__ __launch_bounds__(WG) void mtx_format(const T *X, int64_t ldx, const 
         const int64_t j = (int64_t)s * SEG + threadIdx.x * EPT + k;
         len[k] = 0;
         if (j < C) {
-            v[k] = classify(xr[cols[j]]);
-            if (v[k].status == 0) len[k] = fmt_line<false>(nullptr, (uint64_t)g + 1, (uint64_t)j + 1, is_real<T>::value, v[k]);
+            v[k] = classify<FRAC>(xr[cols[j]]);
+            if (v[k].status == 0) len[k] = fmt_line<false, FRAC>(nullptr, (uint64_t)g + 1, (uint64_t)j + 1, is_real<T>::value, v[k]);
         }
         mine += len[k];
     }
@@ -210,7 +242,7 @@ __global__ __launch_bounds__(WG) void mtx_format(const T *X, int64_t ldx, const 
     for (int k = 0; k < EPT; k++)
         if (len[k]) {
             const int64_t j = (int64_t)s * SEG + threadIdx.x * EPT + k;
-            fmt_line<true>(p, (uint64_t)g + 1, (uint64_t)j + 1, is_real<T>::value, v[k]);
+            fmt_line<true, FRAC>(p, (uint64_t)g + 1, (uint64_t)j + 1, is_real<T>::value, v[k]);
             p += len[k];
         }
     __syncthreads();
@@ -226,23 +258,36 @@ __global__ __launch_bounds__(WG) void mtx_format(const T *X, int64_t ldx, const 
     }
 }
 
-// CALL with T bound to the element type of CYTO_DTYPE_* dt
-#define MTX_DISPATCH(dt, CALL)                                     \
-    switch (dt) {                                                  \
-    case CYTO_DTYPE_F32: { using T = float; CALL; } break;         \
-    case CYTO_DTYPE_F64: { using T = double; CALL; } break;        \
-    case CYTO_DTYPE_U16: { using T = uint16_t; CALL; } break;      \
-    case CYTO_DTYPE_U8: { using T = uint8_t; CALL; } break;        \
-    case CYTO_DTYPE_I32: { using T = int32_t; CALL; } break;       \
-    default: { using T = int64_t; CALL; } break;                   \
+// The statement(s) after frac, with T bound to the element type of CYTO_DTYPE_* dt and FRAC to frac (false for the integer types, whose
+// text has one form)
+#define MTX_DISPATCH(dt, frac, ...)                                                               \
+    switch (dt) {                                                                                 \
+    case CYTO_DTYPE_F32:                                                                          \
+        if (frac) { using T = float; constexpr bool FRAC = true; __VA_ARGS__; }                   \
+        else { using T = float; constexpr bool FRAC = false; __VA_ARGS__; }                       \
+        break;                                                                                    \
+    case CYTO_DTYPE_F64:                                                                          \
+        if (frac) { using T = double; constexpr bool FRAC = true; __VA_ARGS__; }                  \
+        else { using T = double; constexpr bool FRAC = false; __VA_ARGS__; }                      \
+        break;                                                                                    \
+    case CYTO_DTYPE_U16: { using T = uint16_t; constexpr bool FRAC = false; __VA_ARGS__; } break; \
+    case CYTO_DTYPE_U8: { using T = uint8_t; constexpr bool FRAC = false; __VA_ARGS__; } break;   \
+    case CYTO_DTYPE_I32: { using T = int32_t; constexpr bool FRAC = false; __VA_ARGS__; } break;  \
+    default: { using T = int64_t; constexpr bool FRAC = false; __VA_ARGS__; } break;              \
     }
 
 }  // namespace
 
 int cyto_mtx_write(const char *path, int64_t G, int64_t N, const void *x, int64_t ldx, int x_dtype, const int64_t *cols, int64_t C,
                    int64_t block_bytes, int device_id, cyto_mtx_info *info) {
+    return cyto_mtx_write_ex(path, G, N, x, ldx, x_dtype, cols, C, block_bytes, device_id, 0, info);
+}
+
+int cyto_mtx_write_ex(const char *path, int64_t G, int64_t N, const void *x, int64_t ldx, int x_dtype, const int64_t *cols, int64_t C,
+                      int64_t block_bytes, int device_id, int flags, cyto_mtx_info *info) {
     const size_t es = dtype_size(x_dtype);
-    if (!path || !x || !cols || !info || es == 0 || G <= 0 || N <= 0 || C <= 0 || ldx < N || block_bytes < 0 || G > 0x7fffffffll ||
+    const bool frac = (flags & CYTO_TEXT_FRACTIONS) != 0;
+    if ((flags & ~CYTO_TEXT_FRACTIONS) || !path || !x || !cols || !info || es == 0 || G <= 0 || N <= 0 || C <= 0 || ldx < N || block_bytes < 0 || G > 0x7fffffffll ||
         C > 0x7fffffffll)
         return CYTO_ERR_BAD_ARG;
     for (int64_t j = 0; j < C; j++)
@@ -283,7 +328,7 @@ int cyto_mtx_write(const char *path, int64_t G, int64_t N, const void *x, int64_
     // (2) counts, offsets, the values outside the grammar
     const auto t1 = std::chrono::steady_clock::now();
     CYTO_HIP(hipMemsetAsync(scal.p, 0, 16, sg.s));
-    MTX_DISPATCH(x_dtype, hipLaunchKernelGGL(mtx_count<T>, dim3((unsigned)G), dim3(WG), 0, sg.s, dx.as<T>(), ldx, dcols.as<int64_t>(), C,
+    MTX_DISPATCH(x_dtype, frac, hipLaunchKernelGGL((mtx_count<T, FRAC>), dim3((unsigned)G), dim3(WG), 0, sg.s, dx.as<T>(), ldx, dcols.as<int64_t>(), C,
                                              nseg, seg_off.as<int64_t>(), row_bytes.as<int64_t>(), row_nnz.as<int64_t>(),
                                              scal.as<int>() + 2));
     CYTO_HIP(hipGetLastError());
@@ -294,9 +339,9 @@ int cyto_mtx_write(const char *path, int64_t G, int64_t N, const void *x, int64_
     CYTO_HIP(hipMemcpyAsync(hoff.data(), row_off.p, (size_t)(G + 1) * 8, hipMemcpyDeviceToHost, sg.s));
     CYTO_HIP(hipStreamSynchronize(sg.s));
     info->ms_kernels = ms_since(t1);
-    const int flags = (int)(hs[1] & 0xffffffff);
+    const int bad = (int)(hs[1] & 0xffffffff);
     for (int kind : {CYTO_MTX_ERR_NONFINITE, CYTO_MTX_ERR_FRACTION, CYTO_MTX_ERR_MAGNITUDE})
-        if (flags & (1 << kind)) return refuse(kind);
+        if (bad & (1 << kind)) return refuse(kind);
     const int64_t body = hoff[(size_t)G];
     info->nnz = hs[0];
 
@@ -359,7 +404,7 @@ int cyto_mtx_write(const char *path, int64_t G, int64_t N, const void *x, int64_
             CYTO_HIP(hipEventRecord(ev[b], sg.s));
             for (int64_t r0 = ga; r0 < gb; r0 += max_rows) {
                 const int64_t rows = std::min(max_rows, gb - r0);
-                MTX_DISPATCH(x_dtype, hipLaunchKernelGGL(mtx_format<T>, dim3((unsigned)(rows * nseg)), dim3(WG), 0, sg.s, dx.as<T>(), ldx,
+                MTX_DISPATCH(x_dtype, frac, hipLaunchKernelGGL((mtx_format<T, FRAC>), dim3((unsigned)(rows * nseg)), dim3(WG), 0, sg.s, dx.as<T>(), ldx,
                                                          dcols.as<int64_t>(), C, nseg, r0, row_off.as<int64_t>(), seg_off.as<int64_t>(),
                                                          hoff[(size_t)ga], dbuf[b].as<uint8_t>()));
                 CYTO_HIP(hipGetLastError());
@@ -379,18 +424,55 @@ int cyto_mtx_write(const char *path, int64_t G, int64_t N, const void *x, int64_
 
 int cyto_mtx_format_entries(const int64_t *rows, const int64_t *cols, const void *values, int dtype, int64_t n, char *out,
                             int64_t *offsets) {
-    if (n < 0 || !offsets || dtype_size(dtype) == 0 || (n > 0 && (!rows || !cols || !values || !out))) return CYTO_ERR_BAD_ARG;
+    return cyto_mtx_format_entries_ex(rows, cols, values, dtype, n, out, offsets, 0);
+}
+
+int cyto_mtx_format_entries_ex(const int64_t *rows, const int64_t *cols, const void *values, int dtype, int64_t n, char *out,
+                               int64_t *offsets, int flags) {
+    if ((flags & ~CYTO_TEXT_FRACTIONS) || n < 0 || !offsets || dtype_size(dtype) == 0 || (n > 0 && (!rows || !cols || !values || !out)))
+        return CYTO_ERR_BAD_ARG;
+    const bool frac = (flags & CYTO_TEXT_FRACTIONS) != 0;
     uint8_t *o = reinterpret_cast<uint8_t *>(out);
     int64_t at = 0;
     offsets[0] = 0;
     for (int64_t i = 0; i < n; i++) {
         if (rows[i] < 0 || cols[i] < 0) return CYTO_ERR_BAD_ARG;
-        Val v{};
-        bool real = false;
-        MTX_DISPATCH(dtype, (v = classify(static_cast<const T *>(values)[i]), real = is_real<T>::value));
-        if (v.status > 1) return CYTO_ERR_UNSUPPORTED;
-        if (v.status == 0) at += fmt_line<true>(o + at, (uint64_t)rows[i] + 1, (uint64_t)cols[i] + 1, real, v);
+        int len = 0, status = 0;
+        MTX_DISPATCH(dtype, frac, {
+            const Val v = classify<FRAC>(static_cast<const T *>(values)[i]);
+            status = v.status;
+            if (status == 0) len = fmt_line<true, FRAC>(o + at, (uint64_t)rows[i] + 1, (uint64_t)cols[i] + 1, is_real<T>::value, v);
+        });
+        if (status > 1) return CYTO_ERR_UNSUPPORTED;
+        at += len;
         offsets[i + 1] = at;
     }
+    return CYTO_OK;
+}
+
+int cyto_shortest_digits(const void *values, int dtype, int64_t n, uint64_t *digits, int32_t *exp10) {
+    if (n < 0 || (dtype != CYTO_DTYPE_F32 && dtype != CYTO_DTYPE_F64) || (n > 0 && (!values || !digits || !exp10))) return CYTO_ERR_BAD_ARG;
+    for (int64_t i = 0; i < n; i++) {
+        Decimal d{0, 0};
+        if (dtype == CYTO_DTYPE_F32) {
+            const uint32_t b = static_cast<const uint32_t *>(values)[i] & 0x7fffffffu;
+            if (b >= 0x7f800000u) return CYTO_ERR_BAD_ARG;
+            if (b) d = shortest_digits32(b);
+        } else {
+            const uint64_t b = static_cast<const uint64_t *>(values)[i] & 0x7fffffffffffffffull;
+            if (b >= 0x7ff0000000000000ull) return CYTO_ERR_BAD_ARG;
+            if (b) d = shortest_digits64(b);
+        }
+        digits[i] = d.digits;
+        exp10[i] = d.exp10;
+    }
+    return CYTO_OK;
+}
+
+int cyto_text_pow10(int k, uint64_t out[2]) {
+    if (!out || k < POW10_MIN || k > POW10_MAX) return CYTO_ERR_BAD_ARG;
+    const Pow10 g = pow10_entry(k);
+    out[0] = g.hi;
+    out[1] = g.lo;
     return CYTO_OK;
 }

@@ -47,10 +47,11 @@ _MTX_REFUSALS = {_lib.CYTO_MTX_ERR_FRACTION: "non-integer value", _lib.CYTO_MTX_
                  _lib.CYTO_MTX_ERR_MAGNITUDE: "magnitude", _lib.CYTO_MTX_ERR_SQUARE: "square", _lib.CYTO_MTX_ERR_IO: "io"}
 
 
-def _mtx_narrow(x):
+def _mtx_narrow(x, fractions=False):
     """x (one of _MTX_DTYPES) as the narrowest array the device formats to the same text, and its CYTO_DTYPE_*.  Integers: the
     field stays "integer" (uint8 / uint16 / int32 / int64 by range).  float64: float32 when every value is one and lies below 2^24,
-    where both types' shortest digits are the integer's own."""
+    where both types' shortest digits are the integer's own.  fractions: the device then writes a float32 that is no integer by
+    float32's shortest digits (0.1 for the float64 0.10000000149011612), so every value must be an integer as well."""
     to, code = _MTX_DTYPES[x.dtype.name]
     if x.dtype.kind in "iu" and x.size:
         lo, hi = int(x.min()), int(x.max())
@@ -64,12 +65,14 @@ def _mtx_narrow(x):
         if -(1 << 24) < x.min() and x.max() < (1 << 24):     # (False with a NaN: the device refuses it whatever the type)
             x32 = x.astype(np.float32)
             step = max(1, (1 << 24) // x.shape[1])           # (compared in row blocks: array_equal widens its block to float64)
-            if all(np.array_equal(x32[r:r + step], x[r:r + step]) for r in range(0, x.shape[0], step)):
+            if all(np.array_equal(x32[r:r + step], x[r:r + step]) and
+                   (not fractions or np.array_equal(np.trunc(x32[r:r + step]), x32[r:r + step]))
+                   for r in range(0, x.shape[0], step)):
                 return np.ascontiguousarray(x32), _lib.CYTO_DTYPE_F32
     return np.ascontiguousarray(x, dtype=to), code
 
 
-def write_mtx_device(path, matrix_or_frame, columns, device_id=0, block_bytes=0, return_info=False):
+def write_mtx_device(path, matrix_or_frame, columns, device_id=0, block_bytes=0, return_info=False, fractions=False):
     """scipy.io.mmwrite(path, scipy.sparse.coo_matrix(frame.iloc[:, columns])) with the text formatted on the GPU (C ABI:
     cyto_mtx_write; csrc/mtx.hip): the same bytes.  matrix_or_frame: genes x cells, a DataFrame or a 2-D array; columns: the
     positions (not labels) of the cells to write, in file order, repeats allowed.  block_bytes: the most text per device buffer
@@ -79,6 +82,10 @@ def write_mtx_device(path, matrix_or_frame, columns, device_id=0, block_bytes=0,
     integer below 2^53 (2^24 for float32), a square result, a dtype other than int8..int64 / uint8 / uint16 / float32 / float64,
     a frame whose column labels are not unique or whose selected columns have another common dtype than the whole frame, an empty
     result, a path that is not a str.
+
+    fractions=True (C ABI: cyto_mtx_write_ex with CYTO_TEXT_FRACTIONS; save_results passes it): the device writes every finite real
+    value, by the shortest digits that read back as the same value of the matrix's dtype, as scipy does ("1E-1", "2.5",
+    "3.333333333333333E-1", "5E-324"); of the real values only NaN and +-inf ("non-finite value") still go to scipy.
 
     return_info: also return a dict -- "path" ("device" or "scipy"), for a fallback "reason", and for the device "nnz", "bytes",
     "field", "blocks" and the phase times in seconds: narrow_s (the host's choice of the upload dtype), library_s (the whole
@@ -128,12 +135,16 @@ def write_mtx_device(path, matrix_or_frame, columns, device_id=0, block_bytes=0,
     if x.dtype.name not in _MTX_DTYPES:
         return refuse(f"dtype {x.dtype}")
     t = time.perf_counter()
-    x, code = _mtx_narrow(x)
+    x, code = _mtx_narrow(x, fractions)
     info["narrow_s"] = time.perf_counter() - t
     mi = _lib.MtxInfo()
     t = time.perf_counter()
-    st = _lib.lib().cyto_mtx_write(path.encode(), G, N, x.ctypes.data, N, code, columns.ctypes.data, C, int(block_bytes), device_id,
-                                   ctypes.byref(mi))
+    if fractions:
+        st = _lib.lib().cyto_mtx_write_ex(path.encode(), G, N, x.ctypes.data, N, code, columns.ctypes.data, C, int(block_bytes),
+                                          device_id, _lib.CYTO_TEXT_FRACTIONS, ctypes.byref(mi))
+    else:
+        st = _lib.lib().cyto_mtx_write(path.encode(), G, N, x.ctypes.data, N, code, columns.ctypes.data, C, int(block_bytes), device_id,
+                                       ctypes.byref(mi))
     info["library_s"] = time.perf_counter() - t
     if st == _lib.CYTO_ERR_UNSUPPORTED:                                      # nothing is left at `path`
         return refuse(_MTX_REFUSALS.get(mi.reason, str(mi.reason)))
@@ -191,7 +202,7 @@ def csv_header_and_labels(index_labels, column_labels, index_name=None):
 
 
 def write_csv_device(path, matrix_or_frame, columns, index_labels=None, column_labels=None, index_name=None, device_id=0, block_bytes=0,
-                     return_info=False):
+                     return_info=False, fractions=False):
     """out = frame.iloc[:, columns]; out.index = index_labels; out.columns = column_labels; out.index.name = index_name;
     out.to_csv(path) -- with the value fields formatted on the GPU (C ABI: cyto_csv_write; csrc/csv.hip): the same bytes, and the
     selected genes x cells frame is never built on the host.  matrix_or_frame: genes x cells, a DataFrame or a 2-D array; columns:
@@ -206,6 +217,11 @@ def write_csv_device(path, matrix_or_frame, columns, index_labels=None, column_l
     below 2^53 (2^24 for float32) -- found by the device while it counts, also in a late slab --, a dtype other than int8..int64 /
     uint8 / uint16 / float32 / float64, selected columns of more than one dtype, duplicate column labels in the source frame, labels
     that are neither strings nor integers, an empty result, a path that is not a str, a file that cannot be created or written.
+
+    fractions=True (C ABI: cyto_csv_write_ex with CYTO_TEXT_FRACTIONS; save_results passes it): the device writes every finite real
+    value as pandas does, a float64 as repr(float) ("0.0001", "0.3333333333333333", "1e-05", "1.5e+20"), a float32 by float32's own
+    shortest digits in numpy's form ("0.33333334", "1e-04", "1.2345679e+17"); of the real values only NaN and +-inf ("non-finite
+    value") still go to pandas.
 
     return_info: also return a dict -- "path" ("device" or "pandas"), for a fallback "reason", and for the device "bytes", "blocks"
     and the phase times in seconds: labels_s (the host's header and labels), library_s (the whole cyto_csv_write call: device and
@@ -275,8 +291,12 @@ def write_csv_device(path, matrix_or_frame, columns, index_labels=None, column_l
     x = np.ascontiguousarray(x, dtype=to)                    # (a copy for int8 / int16 and for a frame held column-major)
     ci = _lib.CsvInfo()
     t = time.perf_counter()
-    st = _lib.lib().cyto_csv_write(path.encode(), G, N, x.ctypes.data, N, code, picked.ctypes.data, C, header, len(header), labels,
-                                   off.ctypes.data, int(block_bytes), device_id, ctypes.byref(ci))
+    if fractions:
+        st = _lib.lib().cyto_csv_write_ex(path.encode(), G, N, x.ctypes.data, N, code, picked.ctypes.data, C, header, len(header), labels,
+                                          off.ctypes.data, int(block_bytes), device_id, _lib.CYTO_TEXT_FRACTIONS, ctypes.byref(ci))
+    else:
+        st = _lib.lib().cyto_csv_write(path.encode(), G, N, x.ctypes.data, N, code, picked.ctypes.data, C, header, len(header), labels,
+                                       off.ctypes.data, int(block_bytes), device_id, ctypes.byref(ci))
     info["library_s"] = time.perf_counter() - t
     if st == _lib.CYTO_ERR_UNSUPPORTED:                                      # nothing is left at `path`
         return refuse(_CSV_REFUSALS.get(ci.reason, str(ci.reason)))
@@ -290,7 +310,7 @@ def write_csv_device(path, matrix_or_frame, columns, index_labels=None, column_l
 def save_results(output_path, output_prefix, cell_ids_selected, all_cells_save, assigned_locations,
                  cell_type_data, sampling_method, single_cell, device_id=None):
     """post_processing.py:10-116, same arguments, and device_id: None writes matrix.mtx / new_scRNA.csv on the host (scipy / pandas);
-    a device number has write_mtx_device / write_csv_device write them (the same bytes).  Writes
+    a device number has write_mtx_device / write_csv_device write them (the same bytes, fractional values included).  Writes
       <prefix>assigned_locations.csv
       <prefix>assigned_expression/{genes.tsv, barcodes.tsv, matrix.mtx}     (sampling_method "duplicates")
       <prefix>new_scRNA.csv                                                 ("place_holders": the generated cells)
@@ -325,13 +345,13 @@ def save_results(output_path, output_prefix, cell_ids_selected, all_cells_save, 
             genes.reset_index(inplace=True)
             genes.to_csv(os.path.join(out_dir, "genes.tsv"), sep="\t", header=False, index=False)
             pd.Index(df.UniqueCID).to_frame().to_csv(os.path.join(out_dir, "barcodes.tsv"), sep="\t", header=False, index=False)
-            write_mtx_device(os.path.join(out_dir, "matrix.mtx"), all_cells_save, positions, device_id=device_id)
+            write_mtx_device(os.path.join(out_dir, "matrix.mtx"), all_cells_save, positions, device_id=device_id, fractions=True)
     elif device_id is not None and all_cells_save.columns.is_unique:
         positions = np.flatnonzero(~all_cells_save.columns.isin(cell_type_data.index))     # the generated cells, without their frame
         write_csv_device(os.path.join(output_path, f"{output_prefix}new_scRNA.csv"), all_cells_save, positions,
                          index_labels=_strip("GENE_", all_cells_save.index.astype(str)),
                          column_labels=_strip("CELL_", all_cells_save.columns[positions].astype(str)), index_name="",
-                         device_id=device_id)          # (the host branch's list of labels drops the index's name: none here either)
+                         device_id=device_id, fractions=True)   # (the host branch's list of labels drops the index's name: none here either)
     else:
         generated = all_cells_save.loc[:, ~all_cells_save.columns.isin(cell_type_data.index)]
         generated.index = _strip("GENE_", generated.index.astype(str))

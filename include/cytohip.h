@@ -524,6 +524,27 @@ void cyto_table_free(cyto_table *t);
  * and values[i] as a decimal), 1 decimal token (values[i]), 2 outside the token grammar, 3 out of range. */
 int cyto_table_parse_tokens(const char *text, int64_t n, const int64_t *offsets, double *values, int64_t *ints, int8_t *kinds);
 
+/* ---- flags of the two text writers' _ex entry points (cyto_mtx_write_ex, cyto_csv_write_ex and the host hooks).  0: the grammar of
+ * cyto_mtx_write / cyto_csv_write, bit for bit.  Any other bit than those named here: CYTO_ERR_BAD_ARG before a device is touched.
+ * CYTO_TEXT_FRACTIONS: every finite float32 / float64 value is written, by the shortest decimal digits that read back as the same value
+ * of ITS type (among the shortest, those closest to the value): what repr(float), numpy and scipy print.  Let d1 d2 ... dk be those
+ * digits and e the decimal exponent of d1.
+ *   MatrixMarket:   [-]d1[.d2...dk][E<e>], no E part when e = 0, the exponent without '+' or padding: 1E-1, 2.5, 5E-324.
+ *   CSV, float64:   repr(float): for -4 <= e < 16 positional with at least one digit after the point (0.0001, 2.5, 9007199254740992.0),
+ *                   else d1[.d2...dk]e[+-]XX with at least two exponent digits (1e-05, 1.5e+20).
+ *   CSV, float32:   numpy's text of a float32: the same two forms, the scientific one when |v| < 1e-4 or |v| >= 1e16 (by the value:
+ *                   float32(1e-4) lies below 1e-4 and is 1e-04).
+ * The longest texts: 24 bytes for a float64 in either layout, 19 for a float32 in CSV.  Only NaN and +-inf are still refused
+ * (CYTO_*_ERR_NONFINITE); CYTO_*_ERR_FRACTION and CYTO_*_ERR_MAGNITUDE are never reported.  The integer types are not affected. */
+enum { CYTO_TEXT_FRACTIONS = 1 };
+/* The digits alone, on the host (test hooks; no device).  values: n float32 / float64 (CYTO_DTYPE_F32 / _F64), the sign is ignored:
+ * values[i] = digits[i] * 10^exp10[i], digits[i] without a trailing zero, below 10^9 / 10^17; a zero gives (0, 0).  CYTO_ERR_BAD_ARG at
+ * a NaN or an infinity.  It is the function the device calls (csrc/shortest.h). */
+int cyto_shortest_digits(const void *values, int dtype, int64_t n, uint64_t *digits, int32_t *exp10);
+/* out[0], out[1] := the high and low word of the routine's table entry for 10^k, ceil(10^k * 2^(127 - floor(log2(10^k)))),
+ * -292 <= k <= 324 (else CYTO_ERR_BAD_ARG). */
+int cyto_text_pow10(int k, uint64_t out[2]);
+
 /* ---- the assigned-expression MatrixMarket file (cytospace_amd.post_processing.write_mtx_device): what
  * scipy.io.mmwrite(path, coo_matrix(X[:, cols])) writes, byte for byte, formatted on the device.
  * x: G x N host matrix (ldx) of any CYTO_DTYPE_*; cols: C source columns in [0, N), in file order, repeats allowed; G, C < 2^31.
@@ -553,11 +574,16 @@ typedef struct cyto_mtx_info {
 } cyto_mtx_info;
 int cyto_mtx_write(const char *path, int64_t G, int64_t N, const void *x, int64_t ldx, int x_dtype, const int64_t *cols, int64_t C,
                    int64_t block_bytes, int device_id, cyto_mtx_info *info);
+/* The same with flags (CYTO_TEXT_FRACTIONS: no real value but a NaN or an infinity is refused); cyto_mtx_write is flags = 0. */
+int cyto_mtx_write_ex(const char *path, int64_t G, int64_t N, const void *x, int64_t ldx, int x_dtype, const int64_t *cols, int64_t C,
+                      int64_t block_bytes, int device_id, int flags, cyto_mtx_info *info);
 /* The formatter alone, on the host (a test hook): entry i is (rows[i], cols[i], values[i]), 0-based, values of CYTO_DTYPE_* dtype; its
  * line is out[offsets[i], offsets[i + 1]) -- empty for a zero, which the writer skips.  out holds 64 * n bytes, offsets n + 1 words.
  * CYTO_ERR_UNSUPPORTED at the first real value outside the device grammar. */
 int cyto_mtx_format_entries(const int64_t *rows, const int64_t *cols, const void *values, int dtype, int64_t n, char *out,
                             int64_t *offsets);
+int cyto_mtx_format_entries_ex(const int64_t *rows, const int64_t *cols, const void *values, int dtype, int64_t n, char *out,
+                               int64_t *offsets, int flags);
 
 /* ---- the place-holder expression table, <prefix>new_scRNA.csv (cytospace_amd.post_processing.write_csv_device): what pandas'
  * DataFrame.to_csv writes for the genes x selected-cells frame, byte for byte, the value fields formatted on the device (DESIGN.md
@@ -592,10 +618,17 @@ typedef struct cyto_csv_info {
 int cyto_csv_write(const char *path, int64_t G, int64_t N, const void *x, int64_t ldx, int x_dtype, const int64_t *cols, int64_t C,
                    const char *header, int64_t header_len, const char *labels, const int64_t *label_off, int64_t block_bytes,
                    int device_id, cyto_csv_info *info);
+/* The same with flags (CYTO_TEXT_FRACTIONS: no real value but a NaN or an infinity is refused; a slab's text is then bounded by 25
+ * bytes per float64 field and 20 per float32 field); cyto_csv_write is flags = 0. */
+int cyto_csv_write_ex(const char *path, int64_t G, int64_t N, const void *x, int64_t ldx, int x_dtype, const int64_t *cols, int64_t C,
+                      const char *header, int64_t header_len, const char *labels, const int64_t *label_off, int64_t block_bytes,
+                      int device_id, int flags, cyto_csv_info *info);
 /* The field formatter alone, on the host (a test hook): the text of values[i] (CYTO_DTYPE_* dtype), without a separator, is
  * out[sum of lens[0 .. i), + lens[i]).  cap: the bytes of out, at least 20 * n.  CYTO_ERR_UNSUPPORTED at the first real value outside
  * the device grammar (lens[i] := -CYTO_CSV_ERR_* there). */
 int cyto_csv_format_fields(const void *values, int dtype, int64_t n, char *out, int64_t cap, int32_t *lens);
+/* The same with flags; cap is then at least 24 * n. */
+int cyto_csv_format_fields_ex(const void *values, int dtype, int64_t n, char *out, int64_t cap, int32_t *lens, int flags);
 
 /* ---- a MatrixMarket coordinate file read dense (cytospace_amd.common.read_mtx_device): what scipy.io.mmread(path).toarray() holds,
  * parsed and scattered on the device.  The caller parses the banner, the comments and the size line "G C nnz"; the

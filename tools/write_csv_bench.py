@@ -3,12 +3,16 @@ generated columns, DataFrame.to_csv) on the same frame in the same process.
 
   python tools/write_csv_bench.py [--genes 5000] [--cells 8000] [--selected 4000] [--reps 3] [--host-reps 3]
                                   [--big-genes 20000 --big-cells 40000 --big-selected 30000] [--block-bytes 0] [--out DIR]
+                                  [--fractions [--dtype float64|float32]] [--pass-flag]
 
 Input: genes x cells Poisson counts held as float64 (what the place-holder sampler leaves: integer-valued reals), labelled GENE_* /
 CELL_*; the last `selected` cells are the generated ones, as in a place-holder run.  Timed with a host clock around the whole call
 (the device call ends after its last write()), into a temporary directory, after a small warm-up call of each path; the two paths'
 calls alternate.  Legs: both paths at genes x cells (min / median / max, the files compared byte for byte, the device's phase split
 as the median over its calls, and the text bytes per second of kernels_s), and the device alone at the big shape (skipped when 0).
+--fractions: the counts are divided by each cell's size factor (counts per 10 000, what a normalised reference holds: fractional
+values of full precision, zeros kept), held as --dtype, and the device writer is called with fractions=True; the host path is the
+fallback it replaces.  --pass-flag: the integer-valued frame, but fractions=True as save_results passes it.
 One JSON line per leg; with --out they are appended to DIR/write_csv_bench.jsonl."""
 import argparse
 import json
@@ -26,12 +30,15 @@ sys.path.insert(0, ROOT)
 PHASES = ("labels_s", "library_s", "upload_s", "kernels_s", "download_s", "write_s", "total_s")
 
 
-def make_frame(G, N, seed):
+def make_frame(G, N, seed, fractions=False, dtype="float64"):
     import pandas as pd
     rng = np.random.default_rng(seed)
     x = np.empty((G, N), np.float64)
     for g0 in range(0, G, 1000):
         x[g0:g0 + 1000] = rng.poisson(1.5, (min(1000, G - g0), N))
+    if fractions:
+        x *= 1e4 / np.maximum(x.sum(axis=0), 1)
+        x = x.astype(dtype, copy=False)
     return pd.DataFrame(x, index=[f"GENE_{i}" for i in range(G)], columns=[f"CELL_{i}" for i in range(N)], copy=False)
 
 
@@ -51,12 +58,13 @@ def host_path(path, frame, known):
     return {"gather_s": t1 - t, "to_csv_s": t2 - t1, "total_s": t2 - t}
 
 
-def device_path(path, frame, known, block_bytes):
+def device_path(path, frame, known, block_bytes, flag=False):
     from cytospace_amd.post_processing import write_csv_device
     t = time.perf_counter()
     positions = np.flatnonzero(~frame.columns.isin(known))
     info = write_csv_device(path, frame, positions, index_labels=strip(frame.index.astype(str)),
-                            column_labels=strip(frame.columns[positions].astype(str)), block_bytes=block_bytes, return_info=True)
+                            column_labels=strip(frame.columns[positions].astype(str)), block_bytes=block_bytes, return_info=True,
+                            **({"fractions": True} if flag else {}))
     info["call_s"] = time.perf_counter() - t                 # isin and the label stripping included, as save_results pays them
     assert info["path"] == "device", info
     return info
@@ -81,17 +89,17 @@ def digest(path):
             h.update(b)
 
 
-def leg(G, N, C, reps, host_reps, block_bytes, d, seed):
-    frame = make_frame(G, N, seed)
+def leg(G, N, C, reps, host_reps, block_bytes, d, seed, fractions=False, dtype="float64", flag=False):
+    frame = make_frame(G, N, seed, fractions, dtype)
     known = frame.columns[:N - C]
     pd_, ph_ = os.path.join(d, "device.csv"), os.path.join(d, "host.csv")
     dev, host = [], []
     for r in range(max(reps, host_reps)):                    # alternate the two paths
         if r < reps:
-            dev.append(device_path(pd_, frame, known, block_bytes))
+            dev.append(device_path(pd_, frame, known, block_bytes, flag))
         if r < host_reps:
             host.append(host_path(ph_, frame, known))
-    out = {"genes": G, "cells": N, "selected": C, "dtype": "float64", "fields": G * C, "bytes": dev[0]["bytes"], "blocks": dev[0]["blocks"],
+    out = {"genes": G, "cells": N, "selected": C, "dtype": str(frame.dtypes.iloc[0]), "fractions": fractions, "flag": flag, "fields": G * C, "bytes": dev[0]["bytes"], "blocks": dev[0]["blocks"],
            "device_s": spread([i["call_s"] for i in dev]), "device_phases": medians(dev, PHASES)}
     k = out["device_phases"]["kernels_s"]
     out["text_bytes_per_kernel_second"] = round(dev[0]["bytes"] / k) if k > 0 else None
@@ -121,6 +129,9 @@ def main():
     ap.add_argument("--block-bytes", type=int, default=0)
     ap.add_argument("--tmp", default=None, help="directory for the files written (default: the system's temporary directory)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--fractions", action="store_true", help="a fractional frame, written with fractions=True")
+    ap.add_argument("--dtype", default="float64", choices=["float64", "float32"], help="the fractional frame's dtype")
+    ap.add_argument("--pass-flag", action="store_true", help="fractions=True on the integer-valued frame")
     a = ap.parse_args()
     import ctypes
     from cytospace_amd import _lib
@@ -129,7 +140,8 @@ def main():
     d = tempfile.mkdtemp(prefix="write_csv_bench_", dir=a.tmp)
     lines = []
     try:
-        warm = leg(60, 300, 200, 1, 1, 0, d, 7)              # warm-up: library, HIP, kernels, pandas' writer
+        kw = dict(fractions=a.fractions, dtype=a.dtype, flag=a.fractions or a.pass_flag)
+        warm = leg(60, 300, 200, 1, 1, 0, d, 7, **kw)        # warm-up: library, HIP, kernels, pandas' writer
         assert warm["equal"]
         legs = []
         if a.genes and a.cells:
@@ -137,7 +149,7 @@ def main():
         if a.big_genes and a.big_cells:
             legs.append((a.big_genes, a.big_cells, a.big_selected or a.big_cells, a.big_reps, 0, 1))
         for G, N, C, reps, host_reps, seed in legs:
-            res = dict(device=name.value.decode(), **leg(G, N, C, reps, host_reps, a.block_bytes, d, seed))
+            res = dict(device=name.value.decode(), **leg(G, N, C, reps, host_reps, a.block_bytes, d, seed, **kw))
             lines.append(json.dumps(res))
             print(lines[-1], flush=True)
     finally:
