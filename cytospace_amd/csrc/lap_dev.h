@@ -38,7 +38,7 @@ struct LapStatus {
     int numfree;                        // rows still free before the augmentation (jv_chain2, wide_arr, the one-edge kernels)
     int wide_done;                      // searches done, wide solver (wide_aug and the one-edge kernels)
     int lazy_done;                      // searches completed by jv_aug_lazy (== numfree unless it gave up)
-    int pad0_;
+    int wide_embedded;                  // wide_aug<PAR>: 1 = the searches ran in the embedded form (the launch decides: lap_wide.hip, EMB_GATE)
     int ngroups;                        // runs of identical rows (rows_group_ids)
     int pad1_[3];
     long long wide[WC_N];               // WC_*

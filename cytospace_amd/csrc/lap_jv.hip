@@ -469,6 +469,16 @@ struct ColredAppend {
 // keeps counting: a row over the cap is built by the row builder instead).  Column minima, the lowest row on ties, the non-finite
 // flag and pmin / parg are colred_partial's.  Every lane stays for the ballots: past the last quad it re-reads that quad and owns no
 // column.
+// -DCYTO_COLRED_PROBE=1 / 2 / 3 (developer builds that only TIME the pass, profiles/r10_headline_leftovers_step0.txt; the driver hands
+// every row to the row builder behind them): 1 = no appends at all, the ballots kept; 2 = the atomics kept, no stores; 3 = the stores
+// to the positions a count of zero gives, no atomic
+#ifndef CYTO_COLRED_PROBE
+#define CYTO_COLRED_PROBE 0
+#endif
+// workgroups of the pass per CU (the plan in cyto_lap_f32_batch; a developer build may set another)
+#ifndef CYTO_COLRED_PER_CU
+#define CYTO_COLRED_PER_CU 5
+#endif
 __global__ __launch_bounds__(256) void colred_partial_append(int n, int64_t ld, const float *__restrict__ cost, int rows_per_block,
                                                              float *__restrict__ pmin, int32_t *__restrict__ parg,
                                                              int *__restrict__ nonfinite, int nrows, ColredAppend ap) {
@@ -521,8 +531,20 @@ __global__ __launch_bounds__(256) void colred_partial_append(int n, int64_t ld, 
             if (lane == u) { my_tot = tot[u]; my_row = rr[u]; }
         }
         uint32_t old = 0;
+#if CYTO_COLRED_PROBE == 1
+#pragma unroll
+        for (int u = 0; u < RU; u++) asm volatile("" :: "s"(tot[u]));
+        (void)my_tot; (void)my_row; (void)old; (void)lt;
+#else
+#if CYTO_COLRED_PROBE != 3
         if (my_tot) old = (uint32_t)atomicAdd(ap.cnt + my_row, my_tot);
+#endif
         asm volatile("" : "+v"(old) :: "memory");                      // (the one wait: the positions and the next group's loads)
+#if CYTO_COLRED_PROBE == 2
+#pragma unroll
+        for (int u = 0; u < RU; u++) asm volatile("" :: "s"(__builtin_amdgcn_readlane((int)old, u)));
+        (void)lt;
+#else
 #pragma unroll
         for (int u = 0; u < RU; u++) {
             if (!tot[u]) continue;                                     // (wave-uniform)
@@ -536,6 +558,8 @@ __global__ __launch_bounds__(256) void colred_partial_append(int n, int64_t ld, 
                 pos += __popcll(b[u][e]);
             }
         }
+#endif
+#endif
     }
 #pragma unroll
     for (int e = 0; e < VW; e++) {
@@ -813,6 +837,16 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
     const bool fused_gate = fused_knob != 0 && nb == 1 && pl.wide && !jobs[0].rowmap_host && pl.cache.stream == 1 &&
                             n >= (fused_knob >= 2 ? FUSED_S : 32768);
     const int fused_rs = std::min(1024, n / 2);                   // rows sampled for w
+    // The pass with appends waits for a returning atomic per group of four rows, so its time is set by how evenly its waves share the
+    // chip, not by how many there are: the plain pass's 2 048 workgroups are 1.34 rounds of this kernel's six waves per SIMD, and the
+    // second round runs a third full.  Five workgroups per CU -- one round, every CU alike -- measured best at 50 000^2 (2.26 -> 2.04 ms;
+    // six 2.10, four 2.17: profiles/r10_headline_leftovers_step0.txt).  Column minima and the lowest row on ties do not depend on how
+    // the rows are dealt to the blocks (colred_finish takes the blocks in row order with a strict comparison).
+    if (fused_gate) {
+        pl.rowblocks = max(1, min(CYTO_COLRED_PER_CU * pl.cache.cus / pl.colblocks, (n + 15) / 16));
+        pl.rows_per_block = (n + pl.rowblocks - 1) / pl.rowblocks;
+        pl.rowblocks = (n + pl.rows_per_block - 1) / pl.rows_per_block;
+    }
     // ---- stage 1 (every problem, back to back on the stream: full-chip streaming kernels): column reduction, row groups ----
     CYTO_HIP(hipEventRecord(e0, stream));
     for (F32Job &j : jobs) {
@@ -900,6 +934,9 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
                 const ColredAppend ap = {j.f_w, j.f_theta, j.f_cnt, j.f_list};
                 hipLaunchKernelGGL(colred_partial_append, dim3(pl.colblocks, rblocks), dim3(256), 0, stream, n, j.dld, j.dcost, rpb,
                                    j.b_pmin.as<float>(), j.b_parg.as<int32_t>(), &j.st()->nonfinite, nrows, ap);
+#if CYTO_COLRED_PROBE
+                CYTO_HIP(hipMemsetAsync(j.f_cnt, 0, nI + sizeof(int32_t), stream));     // (every row to the row builder)
+#endif
             } else
             hipLaunchKernelGGL(colred_partial<float>, dim3(pl.colblocks, rblocks), dim3(256), 0, stream, n, j.dld, j.dcost, rpb,
                                j.b_pmin.as<float>(), j.b_parg.as<int32_t>(), &j.st()->nonfinite, nrows,
@@ -984,6 +1021,7 @@ static int lap_solve_f32_batch(int n, std::vector<F32Job> &jobs, int device_id, 
         int32_t *d_rowsol = j.b_iws.as<int32_t>();
         float *d_v = j.b_fws.as<float>();
         CYTO_HIP(hipMemcpy(&h, j.st(), sizeof h, hipMemcpyDeviceToHost));
+        if (pl.wide) wide_note_status(h);
         double h_gap[3] = {-1.0, -1.0, -1.0};
         ExactRun ex;
         if (((opts.certify && j.info) || opts.exact) && !h.status) {

@@ -47,6 +47,8 @@ struct WidePlan {
 // whole batch.  ev_cache_done is recorded behind the first cache build, ev_arr_done behind the row reduction.
 int wide_solve_batch(const WidePlan &pl, const std::vector<SolveJob> &jobs, hipStream_t stream, hipEvent_t ev_cache_done,
                      hipEvent_t ev_arr_done);
+// the status block of a finished wide solve, once per solve: what the process-wide counters take from it (cyto_wide_embedded_solves)
+void wide_note_status(const LapStatus &h);
 // the wide solver's fields of cyto_lap_info (the driver has zeroed it)
 void wide_info(cyto_lap_info *info, const LapStatus &h);
 

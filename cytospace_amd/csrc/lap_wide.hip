@@ -53,6 +53,8 @@ namespace cyto {
 //   cache_red       [n][64] the embedded searches' copy of the caches: fl(cache_val - v[cache_col]) per valid entry, kept current by the
 //                   commits; inv_off [n + 1], inv_ent: per column, the cache entries that hold it (bits of its raw cost << 32 |
 //                   row << 6 | slot), CSR.  Null where the embedded form cannot run
+//   emb_longest     the longest inverse list (one word, written by embed_scan), or null.  Not null: the driver has enqueued the
+//                   embedded kernel AND its plain twin, and each decides on the device whether it is the one to run (EMB_GATE)
 //   misc            the status block (lap_dev.h: LapStatus)
 //   same_prev       [n] 1 = the row equals the row before it (runs of identical rows: CytoSPACE repeats a spot's row per slot), or null
 //   seg_sync        shared by the launch, or null: [0] workgroups that asked for fresh caches (zeroed by the driver before every launch
@@ -74,7 +76,8 @@ namespace cyto {
     P(int32_t, freerows) P(int32_t, act0) P(int32_t, act1) P(int32_t, touched) P(int32_t, slot_j) P(float, slot_p)            \
     P(float, slot_c) P(uint32_t, cache_col) P(float, cache_val) P(char, misc) S(long long, max_rounds)                     \
     P(const int32_t, same_prev) P(int32_t, seg_sync) S(int, aug_seg) S(int, aug_waste) S(int, arr_waste) S(int, seg_quorum)   \
-    P(char, sc) S(int, par_groups) P(char, par) P(char, scx) P(float, cache_red) P(const int32_t, inv_off) P(const unsigned long long, inv_ent)
+    P(char, sc) S(int, par_groups) P(char, par) P(char, scx) P(float, cache_red) P(const int32_t, inv_off) P(const unsigned long long, inv_ent)    \
+    P(const int32_t, emb_longest)
 #define WIDE_F_PTR(T, name) T *name;
 #define WIDE_F_VAL(T, name) T name;
 struct WideArgs { WIDE_FIELDS(WIDE_F_PTR, WIDE_F_VAL) };
@@ -1491,7 +1494,7 @@ __device__ __noinline__ void embed_repair(gf32_t *cache_red, gci32_t *inv_off, g
 // keeps the LOWEST workgroup of the LATEST batch -- and RETURNS the word it replaced.  Within a batch a column's word therefore holds the
 // running lowest g of its claimants: an arrival that is no new running minimum sees a smaller g and flags ITSELF; an arrival that is a new
 // running minimum sees the previous one and flags THAT; so, whatever the order of arrival, every claimant of a column but its lowest is
-// flagged (atomic min into P) -- exactly the searches that found "one of my columns carries another key" in a pass of their own behind a
+// flagged (P = the lowest flagged search: a minimum per thread, one atomic min per wave that saw a flag) -- exactly the searches that found "one of my columns carries another key" in a pass of their own behind a
 // grid barrier before.  Same P, same committed prefix, same batches, same discarded searches.  A word of an earlier batch flags nobody.
 // In the same pass the settled columns go to a list (column, ordered distance), compacted by ballot with one LDS atomic per wave and four
 // steps, and to the path links: by column, (the row that labelled it, that row's column) -- rowsol of a path row is changed by no other
@@ -1551,12 +1554,15 @@ __device__ __noinline__ unsigned long long search_end(const WideArgs *__restrict
         const bool have = Tk != ~0ull;
         if (active && !have && tid == 0) { atomicExch(&pc->err, 1); atomicMin(&pc->P[par], g); }
         const uint32_t key = ((uint32_t)batchno << 8) | (uint32_t)(255 - g);
-        // (measured, profiles/r09_batch_end_ab.txt: a deep search that shares thousands of columns with a lower one sends as many
-        //  atomic minima to P's address, 110 us for 3 892 columns; a minimum per thread and one atomic per wave is the next step)
+        // P needs only the LOWEST flagged search: a thread keeps the lowest it has seen in a register, and behind the pass a wave that
+        // saw one sends ONE atomic min (the minimum of minima is the minimum).  (One atomic min per shared column before: a deep search
+        // that shares thousands of columns with a lower one sent as many to P's one address, 110 us for 3 892 columns,
+        // profiles/r09_batch_end_ab.txt.)
+        uint32_t fmin = PAR_GMAX + 1;
         auto flag = [&](uint32_t old) {                           // old: what a claim's atomic max returned
             if ((old >> 8) == (uint32_t)batchno && old != key) {
-                const int go = 255 - (int)(old & 255u);
-                atomicMin(&pc->P[par], g > go ? g : go);
+                const uint32_t go = 255u - (old & 255u);
+                fmin = umin32(fmin, (uint32_t)g > go ? (uint32_t)g : go);
             }
         };
         if (have) {
@@ -1598,6 +1604,15 @@ __device__ __noinline__ unsigned long long search_end(const WideArgs *__restrict
                     }
             }
             if (tid == 0) flag(atomicMax(sv.claim + sink, key));
+        }
+        // (every lane of every wave arrives here: the trips above are the same in every thread.  The wave waits until its atomic has
+        //  been performed: thread 0's release in par_barrier covers wave 0's own operations only, and the workgroup barrier in front
+        //  of it is compiled without a wait for the other waves' outstanding stores and atomics -- the gfx950 assembly shows
+        //  s_waitcnt lgkmcnt(0); s_barrier there.  One round trip, in the waves that saw a flag, instead of one per shared column)
+        const uint32_t wfmin = wave_min_u32(fmin);
+        if (wfmin <= (uint32_t)PAR_GMAX && lane == 0) {
+            atomicMin(&pc->P[par], (int)wfmin);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         FS_LAP(FS_CLAIM)
         par_barrier(pc, G, pgen);
@@ -1777,6 +1792,7 @@ __device__ __noinline__ unsigned long long search_end(const WideArgs *__restrict
     return (unsigned long long)(uint32_t)nhop | ((unsigned long long)(uint32_t)Pb << 32) | ((unsigned long long)(commit ? 1 : 0) << 48);
 }
 
+constexpr int EMB_GATE = 4 * KCU;       // longest inverse list the embedded form runs with (a commit rewrites a list per repriced column)
 template <bool VLDS, bool CLDS, bool PAR, bool EMB = false>
 __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batch) {
     static_assert(!EMB || (PAR && !VLDS), "the embedded form: several searches at once, prices in global memory");
@@ -1787,6 +1803,11 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
     if (PAR && (blockIdx.x % pstride)) return;
     const int g = PAR ? uni((int)(blockIdx.x / pstride)) : 0;
     const WideArgs a = load_wide_args(batch, PAR ? 0 : blockIdx.x);
+    // The gate of the embedded form, on the device: a column in thousands of caches (few cell types) -- a deep search would rewrite most
+    // of cache_red.  The driver has enqueued both forms behind the build of the inverse lists; the one whose turn it is not ends here,
+    // before its first barrier and before it touches the status block or the control block.  (The driver read the word back and chose
+    // before: the chip waited for the host, and the search kernel was enqueued onto an idle chip.)
+    if (PAR && a.emb_longest && (uni(ld_sc1(a.emb_longest)) <= EMB_GATE) != EMB) return;
     const int n = a.n, tid = threadIdx.x, lane = tid & 63, w = uni((int)(threadIdx.x >> 6));
     const int nblk = (n + 63) / 64, nw32 = (n + 31) / 32;
     // the search's own arrays: the problem's (one search at a time) or this workgroup's (PAR)
@@ -2343,6 +2364,7 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
         if (a.seg_sync) a.seg_sync[1 + (PAR ? 0 : blockIdx.x)] = err ? 0 : numfree - f;
         long long *tmr = st->timers;
         tmr[WT_AUG_ROUNDS_TICKS] += t_rounds; tmr[WT_AUG_VERIFY_TICKS] += t_verify; tmr[WT_AUG_FINISH_TICKS] += t_finish; tmr[WT_AUG_TRIVIAL_TICKS] += t_triv;
+        if (PAR) st->wide_embedded = EMB ? 1 : 0;
         if (PAR) { tmr[WT_PAR_BATCHES] = ld_sc1(reinterpret_cast<unsigned long long *>(&pc->c_batches)); tmr[WT_PAR_DISCARDED] = ld_sc1(reinterpret_cast<unsigned long long *>(&pc->c_discarded)); }
     }
 }
@@ -2684,7 +2706,6 @@ static int wide_launch_arr(const WideArgs *d_args, int nb, int n, hipStream_t st
 
 // ---- the embedded form's arrays, built by the whole chip between the last cache build and the searches ----
 // cache_red [n][KC] | inv_off [n + 1] | counts [n + 1] (the last word: the longest list) | block sums [2 x blocks] | rank [n][KC] | inv_ent [n * KCU]
-constexpr int EMB_GATE = 4 * KCU;       // longest inverse list the embedded form is launched with (a commit rewrites a list per repriced column)
 constexpr int EMB_SB = 256;             // columns per workgroup of the scan
 static size_t emb_a256(size_t b) { return (b + 255) / 256 * 256; }
 static int emb_blocks(int n) { return (n + EMB_SB - 1) / EMB_SB; }
@@ -2862,12 +2883,13 @@ int wide_solve_batch(const WidePlan &pl, const std::vector<SolveJob> &jobs, hipS
         const size_t emb_off = ((scx_off + wide_sc_ext_bytes(n) + 255) / 256) * 256;
         if ((rc = j.state->alloc(emb_cand ? emb_off + wide_embed_bytes(n) : scx_off + wide_sc_ext_bytes(n), stream))) return rc;
         WideArgs &wa = h_wa[(size_t)k];
-        wa.cache_red = nullptr; wa.inv_off = nullptr; wa.inv_ent = nullptr;
+        wa.cache_red = nullptr; wa.inv_off = nullptr; wa.inv_ent = nullptr; wa.emb_longest = nullptr;
         if (emb_cand) {
             char *eb = j.state->as<char>() + emb_off;
             wa.cache_red = reinterpret_cast<float *>(eb);
             wa.inv_off = reinterpret_cast<int32_t *>(eb + emb_a256((size_t)n * KC * 4));
             wa.inv_ent = reinterpret_cast<unsigned long long *>(eb + emb_off_ent(n));
+            if (embed_knob == 1) wa.emb_longest = emb_counts(wa, n) + n;        // (the gate: both forms are enqueued, the device chooses)
         }
         wa.n = n; wa.ld = j.ld; wa.cost = j.cost; wa.rowmap = j.rowmap;
         wa.v = j.fws; wa.u = j.fws + n; wa.cassign = j.fws + 3 * (int64_t)n;
@@ -2950,18 +2972,14 @@ int wide_solve_batch(const WidePlan &pl, const std::vector<SolveJob> &jobs, hipS
         bool embed = false;
         if (parg > 0 && h_wa[0].cache_red) {                   // (one launch runs all searches: the caches are not rebuilt behind this)
             if ((rc = wide_build_embedded(h_wa[0], n, stream))) return rc;
-            embed = embed_knob >= 2;
-            if (!embed) {                                      // the gate: a column in thousands of caches (few cell types) -- a deep search would rewrite most of the array
-                int32_t longest = 0;
-                CYTO_HIP(hipMemcpyAsync(&longest, emb_counts(h_wa[0], n) + n, sizeof longest, hipMemcpyDeviceToHost, stream));
-                CYTO_HIP(hipStreamSynchronize(stream));
-                embed = longest <= EMB_GATE;
-            }
+            embed = true;                                      // (knob 2: always; knob 1: where the gate allows -- wide_aug reads it)
         }
         CYTO_HIP(hipMemsetAsync(d_sync.p, 0, sizeof(int32_t), stream));
         if ((rc = wide_launch_aug(d_wa.as<WideArgs>(), nl, n, stream, parg, embed))) return rc;
-        if (embed) g_embedded_solves.fetch_add(1);
-        if (parg > 0) { CYTO_HIP(hipStreamSynchronize(stream)); break; }
+        // the gate (emb_longest): the plain twin right behind the embedded kernel, and one of the two returns at once.  Which one ran
+        // comes back in the status block (LapStatus::wide_embedded: wide_note_status)
+        if (embed && h_wa[0].emb_longest && (rc = wide_launch_aug(d_wa.as<WideArgs>(), nl, n, stream, parg, false))) return rc;
+        if (parg > 0) { CYTO_HIP(hipStreamSynchronize(stream)); break; }    // (the slot of g_par_busy is held until both have drained)
         CYTO_HIP(hipMemcpyAsync(h_sync.data(), d_sync.p, sizeof(int32_t) * ((size_t)nl + 1), hipMemcpyDeviceToHost, stream));
         CYTO_HIP(hipStreamSynchronize(stream));                // (d_wa is read by the kernels until here)
         bool done = true;
@@ -2970,6 +2988,8 @@ int wide_solve_batch(const WidePlan &pl, const std::vector<SolveJob> &jobs, hipS
     }
     return CYTO_OK;
 }
+
+void wide_note_status(const LapStatus &h) { if (h.wide_embedded) g_embedded_solves.fetch_add(1); }
 
 void wide_info(cyto_lap_info *info, const LapStatus &h) {
     const long long *wc = h.wide, *tm = h.timers;       // (timers: diagnostics for tools/wide_large.py; 100 MHz ticks)
