@@ -144,7 +144,7 @@ def lib():
         if hasattr(L, "cyto_wide_embedded_solves"):          # (absent from older A/B builds loaded through CYTOHIP_LIB)
             L.cyto_wide_embedded_solves.argtypes = []
             L.cyto_wide_embedded_solves.restype = ctypes.c_longlong
-        for name in ("cyto_fused_cache_solves", "cyto_fused_cache_fallback_rows"):
+        for name in ("cyto_fused_cache_solves", "cyto_fused_cache_fallback_rows", "cyto_wide_aborted_searches"):
             if hasattr(L, name):                             # (absent from older A/B builds loaded through CYTOHIP_LIB)
                 getattr(L, name).argtypes = []
                 getattr(L, name).restype = ctypes.c_longlong
@@ -289,6 +289,12 @@ def fused_cache_fallback_rows():
 def wide_embedded_solves():
     """Solves of this process whose searches ran in the wide solver's embedded form (cyto_wide_embedded_solves)."""
     return int(lib().cyto_wide_embedded_solves())
+
+
+def wide_aborted_searches():
+    """Searches of this process that several-searches-at-once solves ended early, because a lower search of their batch was flagged
+    or they were themselves (cyto_wide_aborted_searches; knob CYTO_AUG_ABORT=0: none)."""
+    return int(lib().cyto_wide_aborted_searches())
 
 
 def cache_poison(byte):

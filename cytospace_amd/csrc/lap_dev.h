@@ -40,7 +40,8 @@ struct LapStatus {
     int lazy_done;                      // searches completed by jv_aug_lazy (== numfree unless it gave up)
     int wide_embedded;                  // wide_aug<PAR>: 1 = the searches ran in the embedded form (the launch decides: lap_wide.hip, EMB_GATE)
     int ngroups;                        // runs of identical rows (rows_group_ids)
-    int pad1_[3];
+    int wide_aborted;                   // wide_aug<PAR>: searches ended early because they could no longer be committed (cyto_wide_aborted_searches)
+    int pad1_[2];
     long long wide[WC_N];               // WC_*
     long long timers[WT_N];             // WT_*
     unsigned char arr[128];             // wide_arr's phase machine (lap_wide.hip: ArrHead)

@@ -63,6 +63,7 @@ namespace cyto {
 //   scx             the phase machine's own arrays (wide_sc_ext_bytes(n), 256-byte aligned; the first wide_sc_ones_bytes(n) all-ones, the rest zero):
 //                   ScMem
 //   par_groups, par searches of one problem that run at once on as many workgroups (0 / 1: one at a time) and their state (ParCtl)
+//   aug_abort       several searches at once: 1 = a search that can no longer be committed ends early
 //   arr_waste       wide_arr: full-row bids (with their cache refresh) of one launch after which the list rounds pause (aug_seg == 0)
 //   aug_seg         when a launch of wide_aug returns to the driver for fresh row caches: -1 never, k > 0 after k searches, 0 when
 //                   its full-row relaxations reach aug_waste or seg_quorum workgroups of the launch have asked (LapStatus::wide_done holds the
@@ -77,7 +78,7 @@ namespace cyto {
     P(float, slot_c) P(uint32_t, cache_col) P(float, cache_val) P(char, misc) S(long long, max_rounds)                     \
     P(const int32_t, same_prev) P(int32_t, seg_sync) S(int, aug_seg) S(int, aug_waste) S(int, arr_waste) S(int, seg_quorum)   \
     P(char, sc) S(int, par_groups) P(char, par) P(char, scx) P(float, cache_red) P(const int32_t, inv_off) P(const unsigned long long, inv_ent)    \
-    P(const int32_t, emb_longest)
+    P(const int32_t, emb_longest) S(int, aug_abort)
 #define WIDE_F_PTR(T, name) T *name;
 #define WIDE_F_VAL(T, name) T name;
 struct WideArgs { WIDE_FIELDS(WIDE_F_PTR, WIDE_F_VAL) };
@@ -1302,6 +1303,7 @@ struct AugShared {
     int nhop;                      // edges of the path being flipped
     int nset;                      // PAR: entries of this search's list of settled columns
     int scans;
+    int ab, nab;                   // PAR: this search was aborted in its rounds (search_end reads it); searches of this workgroup aborted so far
     int st_row[64], st_col[64];    // one-edge searches: their results, stored to global memory 64 at a time
     float st_val[64];
     // full-row relaxations of a round (an owner whose cache could not certify): queued by the wave that settled the column, done by the
@@ -1330,15 +1332,16 @@ struct ParCtl {
     unsigned int bar_arrive, bar_gen;
     int P[2], nplog[2], nolog[2];          // per batch parity: first conflicting search, entries of the two change logs
     int err, pad_;
-    long long c_relax, c_hops, c_proc, c_dense, c_rounds, c_verify, c_batches, c_discarded;
+    long long c_relax, c_hops, c_proc, c_dense, c_rounds, c_verify, c_batches, c_discarded, c_aborted;
 };
 static_assert(sizeof(ParCtl) <= 256, "control block");
 constexpr int PAR_GMAX = 64;
 // -DCYTO_AUG_FIN_SPLIT (a developer build, tools/fin_split.py): the end of every batch by parts, per workgroup -- thread 0's clock at
 // the boundaries, with a workgroup barrier in front of every stamp (so the parts of this build are a little longer than the plain one's)
 #ifdef CYTO_AUG_FIN_SPLIT
-constexpr int FS_MAXB = 2048, FS_G = 16, FS_NP = 14;
-enum { FS_CLAIM, FS_WAIT1, FS_CHECK, FS_WAIT2, FS_UPDATE, FS_WALK, FS_COST, FS_RESET, FS_WAIT3, FS_REPAIR, FS_NTOUCH, FS_SETTLED, FS_HOPS, FS_ARRIVE };
+constexpr int FS_MAXB = 2048, FS_G = 16, FS_NP = 15;
+enum { FS_CLAIM, FS_WAIT1, FS_CHECK, FS_WAIT2, FS_UPDATE, FS_WALK, FS_COST, FS_RESET, FS_WAIT3, FS_REPAIR, FS_NTOUCH, FS_SETTLED, FS_HOPS, FS_ARRIVE,
+       FS_ABORTED };
 __device__ long long g_fs[FS_MAXB][FS_G][FS_NP];
 #define FS_OK (PAR && batchno - 1 < FS_MAXB && g < FS_G)
 #define FS_BEGIN() { if (PAR && tid == 0) { fs_mark = wall_clock64(); if (FS_OK) g_fs[batchno - 1][g][FS_ARRIVE] = fs_mark; } }
@@ -1488,7 +1491,7 @@ __device__ __noinline__ void embed_repair(gf32_t *cache_red, gci32_t *inv_off, g
 // THE END OF A SEARCH (wide_aug): [PAR: claims, the conflict-free prefix of the batch;] price update and path, the new owners, reset.
 // Out of line like embed_repair, and for the same reason: the search rounds must keep the registers they have.  The kernel's LDS arrives
 // as typed pointers (what goes through them stays LDS instructions), the argument block is read again.
-// Returns hops of the flipped path | P of the batch << 32 | (this search was committed) << 48.
+// Returns hops of the flipped path | P of the batch << 32 | (this search was committed) << 48 | (it was aborted in its rounds) << 49.
 //
 // PAR, the claims: every column a search settled (label below its end's) and its sink get an atomic max of (batch << 8 | 255 - g), which
 // keeps the LOWEST workgroup of the LATEST batch -- and RETURNS the word it replaced.  Within a batch a column's word therefore holds the
@@ -1522,6 +1525,9 @@ __device__ __noinline__ unsigned long long search_end(const WideArgs *__restrict
     const int g = uni(g_), fr = uni(fr_), batchno = uni(batchno_);
     unsigned pgen = uni(pgen_);
     const bool active = uni(active_) != 0;
+    // (PAR, AugShared::ab: the search was ABORTED in its rounds -- a lower search of the batch is flagged, or this one is: it has no end,
+    //  claims nothing, commits nothing, resets what it touched and meets the batch's barriers like any discarded search.  No error.)
+    const bool aborted = PAR && active && uni(s.ab) != 0;
     const WideArgs a = load_wide_args(batch, PAR ? 0 : blockIdx.x);
     const int n = a.n, tid = threadIdx.x, lane = tid & 63, w = uni((int)(threadIdx.x >> 6));
     const int nblk = (n + 63) / 64, nw32 = (n + 31) / 32;
@@ -1541,7 +1547,7 @@ __device__ __noinline__ unsigned long long search_end(const WideArgs *__restrict
 #ifdef CYTO_AUG_FIN_SPLIT
     long long fs_mark = 0;
 #endif
-    const unsigned long long Tk = active ? uni((unsigned long long)s.T) : ~0ull;
+    const unsigned long long Tk = active && !aborted ? uni((unsigned long long)s.T) : ~0ull;
     const uint32_t Dord = (uint32_t)(Tk >> 32);
     const float D = ord2f(Dord);
     const int sink = (int)lid_of(Tk);
@@ -1552,7 +1558,9 @@ __device__ __noinline__ unsigned long long search_end(const WideArgs *__restrict
     FS_BEGIN()
     if (PAR) {
         const bool have = Tk != ~0ull;
-        if (active && !have && tid == 0) { atomicExch(&pc->err, 1); atomicMin(&pc->P[par], g); }
+        // (an aborted search saw P <= g or sent it: once more, from the thread whose release the barrier below waits for)
+        if (active && !have && tid == 0) { if (!aborted) atomicExch(&pc->err, 1); atomicMin(&pc->P[par], g); }
+        FS_SET(FS_ABORTED, aborted ? 1 : 0)
         const uint32_t key = ((uint32_t)batchno << 8) | (uint32_t)(255 - g);
         // P needs only the LOWEST flagged search: a thread keeps the lowest it has seen in a register, and behind the pass a wave that
         // saw one sends ONE atomic min (the minimum of minima is the minimum).  (One atomic min per shared column before: a deep search
@@ -1789,7 +1797,8 @@ __device__ __noinline__ unsigned long long search_end(const WideArgs *__restrict
     __syncthreads();
     FS_SET(FS_NTOUCH, nt)
     FS_LAP(FS_RESET)
-    return (unsigned long long)(uint32_t)nhop | ((unsigned long long)(uint32_t)Pb << 32) | ((unsigned long long)(commit ? 1 : 0) << 48);
+    return (unsigned long long)(uint32_t)nhop | ((unsigned long long)(uint32_t)Pb << 32) | ((unsigned long long)(commit ? 1 : 0) << 48) |
+           ((unsigned long long)(aborted ? 1 : 0) << 49);
 }
 
 constexpr int EMB_GATE = 4 * KCU;       // longest inverse list the embedded form runs with (a commit rewrites a list per repriced column)
@@ -1853,7 +1862,7 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
         }
     }
     if (tid == 0) { s.waste = 0; s.stop = 0; }
-    if (tid == 0) { s.T = ~0ull; s.ntouch = 0; s.any[0] = 0; s.any[1] = 0; s.any[2] = 0; s.npk[0] = 0; s.npk[1] = 0; s.npk[2] = 0; s.fail = 0; s.anydense = 0; s.rootdense = 0; s.doroot = 0; s.f = f0; s.err = 0; s.scans = 0; s.nset = 0; }
+    if (tid == 0) { s.T = ~0ull; s.ntouch = 0; s.any[0] = 0; s.any[1] = 0; s.any[2] = 0; s.npk[0] = 0; s.npk[1] = 0; s.npk[2] = 0; s.fail = 0; s.anydense = 0; s.rootdense = 0; s.doroot = 0; s.f = f0; s.err = 0; s.scans = 0; s.nset = 0; s.ab = 0; s.nab = 0; }
     __syncthreads();
     auto getv = [&](int j) -> float { return VLDS ? s_v[j] : ld_sc1(a.v + j); };
     auto getcs = [&](int j) -> int {
@@ -1902,6 +1911,14 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
     bool announced = false;
     int fbase = 0, batchno = 1, perr = 0;                        // PAR: first free row of the batch, batch number (claim keys), error seen
     long long c_batches = 0, c_discarded = 0;
+    // PAR, ending a search that can no longer be committed: once per round wave 0 reads the batch's P -- the lowest flagged
+    // search so far, which only falls -- and at P <= g raises AUG_ABORT in the round's pick counter, the word every wave reads behind the
+    // round's barrier anyway (a word of its own there cost every round 8 %: coop_dense_rows).  No store and no atomic in a round that
+    // does not abort; no barrier, no wait: the workgroup only reaches the batch's first barrier sooner.
+    // (What the rounds carry for it is ONE scalar: the kernel sits at its register cap and its allocation follows everything that lives
+    //  across the round loop -- "this search was aborted" travels through AugShared::ab, the count of aborted searches through ::nab.)
+    constexpr int AUG_ABORT = 1 << 30;
+    const int gthr = PAR && a.aug_abort ? g : -1;                // (knob off: P <= -1 never holds)
     for (;;) {
         // ---- wave 0 disposes of the searches that end at once: the free row's best cached column is unassigned and its
         // cache certifies that (no column settled, no price changes: the path is one edge) ----
@@ -2036,7 +2053,7 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
                     ph = (ph + 1) % 3;
                     c_rounds++;
                     wact = np0 > 6 ? WNW : 4;
-                    nd = npd0 >> 16;
+                    nd = PAR && (npd0 & AUG_ABORT) ? -1 : npd0 >> 16;        // (-1: the search is aborted)
                     if (!any0 || nd) break;
                     continue;
                 }
@@ -2081,6 +2098,8 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
                     pjx[q] = pk[q] ? pj[q] : 0;
                     lab_r[q] = ld_sc1(lbl + pjx[q]); ca_r[q] = ld_sc1(a.cassign + pjx[q]);
                 }
+                int p_r = PAR_GMAX + 1;                              // (the batch's P: in flight with the labels, looked at behind them)
+                if (PAR && w == 0) p_r = ld_sc1(&pc->P[batchno & 1]);
                 // ... and with them the labels of the dirty columns of the blocks the wave took from in the LAST round: the new
                 // minimum of such a block is not on any round's critical path this way (it used to be a third round trip, behind a
                 // second barrier).  Safe against the offers that go on meanwhile: the minimum was voided at the pick (store), the
@@ -2113,6 +2132,7 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
                     lab[q] = pk[q] ? uni(lab_r[q]) : ~0ull; ca[q] = uni(ca_r[q]); vp[q] = uni(vp_r[q]);
                     if (!pk[q]) { col[q] = COLSENT; oi[q] = 0; }
                 }
+                if (PAR && w == 0 && uni(p_r) <= gthr && lane == 0) atomicOr(&s.npk[ph], AUG_ABORT);
                 unsigned long long old[AP], co[AP];
                 bool off[AP], dn[AP];
                 float vc[AP];
@@ -2168,7 +2188,7 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
                     const float h = (ca[q] - vp[q]) - ord2f(dord);
                     if (n >= COOP_MIN_N) {                         // a long row: by the whole workgroup, behind the round's barrier (coop_dense_rows)
                         if (lane == 0) {
-                            const int e = atomicAdd(&s.npk[ph], 1 << 16) >> 16;
+                            const int e = (atomicAdd(&s.npk[ph], 1 << 16) >> 16) & 0x3FFF;     // (AUG_ABORT may be set above the count)
                             s.st_row[e] = oi[q]; s.st_row[32 + e] = pj[q]; s.st_col[e] = (int)dord; s.st_col[32 + e] = (int)kq; s.st_val[e] = h;
                         }
                     } else {
@@ -2205,10 +2225,16 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
                 ph = (ph + 1) % 3;
                 c_rounds++;
                 wact = np > 6 ? WNW : 4;
-                nd = npd >> 16;
+                nd = PAR && (npd & AUG_ABORT) ? -1 : npd >> 16;
                 if (!any || nd) break;
             }
-            if (nd) {                                                // (outside the round loop: its code must not weigh on the rounds)
+            if (PAR && nd < 0) {                                     // aborted: what the round queued is dropped with the search
+                AUG_LAP(t_rounds)
+                if (tid == 0) s.ab = 1;
+                __syncthreads();                                     // (search_end reads it)
+                break;
+            }
+            if (nd) {                                              // (outside the round loop: its code must not weigh on the rounds)
                 coop_dense_rows<VLDS>(&s, nd, a.cost, a.rowmap, a.ld, n, w, lane, lbl, tch, dirty, bmin, asg, s_v, a.v);
                 continue;
             }
@@ -2262,6 +2288,12 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
         // (search_end, out of line; PAR: it meets the launch at one grid barrier)
         const unsigned long long er = uni(search_end<VLDS, CLDS, PAR>(batch, (lds_aug_t *)&s, (lds_u64_t *)w_smem, g, fr, batchno, pgen, active ? 1 : 0));
         if (PAR) pgen++;
+        if (PAR && ((er >> 49) & 1)) {                            // aborted: the rounds were left in mid-flight -- no rebuild is due, the round flags start clean
+#pragma unroll
+            for (int q = 0; q < AP; q++) rb[q] = -1;
+            wact = 4;
+            if (tid == 0) { s.any[0] = 0; s.any[1] = 0; s.any[2] = 0; s.npk[0] = 0; s.npk[1] = 0; s.npk[2] = 0; s.ab = 0; s.nab++; }
+        }
         const bool commit = (er >> 48) & 1;
         const int Pb = (int)((er >> 32) & 0xFFFFu);
         const int par = batchno & 1;
@@ -2327,6 +2359,7 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
             atomicAdd(reinterpret_cast<unsigned long long *>(&pc->c_proc), (unsigned long long)proc);
             atomicAdd(reinterpret_cast<unsigned long long *>(&pc->c_dense), (unsigned long long)dn);
             atomicAdd(reinterpret_cast<unsigned long long *>(&pc->c_discarded), (unsigned long long)c_discarded);
+            if (s.nab) atomicAdd(reinterpret_cast<unsigned long long *>(&pc->c_aborted), (unsigned long long)s.nab);
             if (g == 0) { pc->c_rounds = c_rounds; pc->c_verify = c_verify; pc->c_batches = c_batches; }
         }
         par_barrier(pc, G, pgen);
@@ -2365,6 +2398,7 @@ __global__ __launch_bounds__(WT) void wide_aug(const WideArgs *__restrict__ batc
         long long *tmr = st->timers;
         tmr[WT_AUG_ROUNDS_TICKS] += t_rounds; tmr[WT_AUG_VERIFY_TICKS] += t_verify; tmr[WT_AUG_FINISH_TICKS] += t_finish; tmr[WT_AUG_TRIVIAL_TICKS] += t_triv;
         if (PAR) st->wide_embedded = EMB ? 1 : 0;
+        if (PAR) st->wide_aborted = (int)ld_sc1(reinterpret_cast<unsigned long long *>(&pc->c_aborted));
         if (PAR) { tmr[WT_PAR_BATCHES] = ld_sc1(reinterpret_cast<unsigned long long *>(&pc->c_batches)); tmr[WT_PAR_DISCARDED] = ld_sc1(reinterpret_cast<unsigned long long *>(&pc->c_discarded)); }
     }
 }
@@ -2787,6 +2821,7 @@ static int wide_build_embedded(const WideArgs &wa, int n, hipStream_t stream) {
     return CYTO_OK;
 }
 static std::atomic<long long> g_embedded_solves{0};    // solves of this process whose searches ran in the embedded form
+static std::atomic<long long> g_aborted_searches{0};   // searches of this process that several-searches-at-once solves ended early
 
 // which of the searches' arrays live in LDS
 // (developer knob, read once per process: CYTO_AUG_LDS = 2 or unset: by size; 1: owners in LDS, prices global -- what n > ~24 000
@@ -2917,6 +2952,9 @@ int wide_solve_batch(const WidePlan &pl, const std::vector<SolveJob> &jobs, hipS
         CYTO_HIP(hipMemsetAsync(wa.scx, 0, wide_sc_ext_bytes(n), stream));
         CYTO_HIP(hipMemsetAsync(wa.scx, 0xFF, wide_sc_ones_bytes(n), stream));     // (the machine's bid words and lowest-bid arrays)
         wa.par_groups = parg; wa.par = nullptr;
+        // (developer knob, read once per process: CYTO_AUG_ABORT = 1 or unset: searches that can no longer be committed end early; 0: they
+        //  run to their ends -- same batches, same results: tests/test_wide_abort_gpu.py, the A/B of profiles/r11_doomed_ab.txt)
+        wa.aug_abort = CYTO_KNOB("CYTO_AUG_ABORT").set ? (CYTO_KNOB("CYTO_AUG_ABORT").value != 0 ? 1 : 0) : 1;
         if (parg > 0) {
             const size_t np_ = ((size_t)n + 63) & ~(size_t)63;
             wa.par = j.state->as<char>() + par_off;
@@ -2989,7 +3027,10 @@ int wide_solve_batch(const WidePlan &pl, const std::vector<SolveJob> &jobs, hipS
     return CYTO_OK;
 }
 
-void wide_note_status(const LapStatus &h) { if (h.wide_embedded) g_embedded_solves.fetch_add(1); }
+void wide_note_status(const LapStatus &h) {
+    if (h.wide_embedded) g_embedded_solves.fetch_add(1);
+    if (h.wide_aborted > 0) g_aborted_searches.fetch_add(h.wide_aborted);
+}
 
 void wide_info(cyto_lap_info *info, const LapStatus &h) {
     const long long *wc = h.wide, *tm = h.timers;       // (timers: diagnostics for tools/wide_large.py; 100 MHz ticks)
@@ -3009,6 +3050,7 @@ void wide_info(cyto_lap_info *info, const LapStatus &h) {
 }  // namespace cyto
 
 extern "C" long long cyto_wide_embedded_solves(void) { return cyto::g_embedded_solves.load(); }
+extern "C" long long cyto_wide_aborted_searches(void) { return cyto::g_aborted_searches.load(); }
 
 #ifdef CYTO_AUG_FIN_SPLIT
 // the batch ends of the solves since the last call, by parts: out[batch][workgroup][part] in 100-MHz ticks (tools/fin_split.py); then cleared

@@ -42,6 +42,10 @@ int cyto_abi_sizes(size_t *lap_info, size_t *lap_opts, size_t *assign_info, size
 /* Solves of this process whose searches ran in the wide solver's embedded form (one problem, several searches at once, prices in
  * global memory: DESIGN 4.1a) -- a process-wide count, so that a test can tell which form ran; it is not part of cyto_lap_info. */
 long long cyto_wide_embedded_solves(void);
+/* Searches of this process that several-searches-at-once solves ended before their ends, because a lower search of their batch was
+ * already flagged (0 with the developer knob CYTO_AUG_ABORT=0).  Process-wide count, for tests and tools; every such
+ * search is also counted in cyto_lap_info.wide_par_discarded. */
+long long cyto_wide_aborted_searches(void);
 /* Float32 solves of this process whose first row caches came from the column reduction's own pass (one problem per
  * call, no row map, from 32 768 rows on), and the rows of those solves that the row builder swept all the same (the rows the lists
  * could not certify; every row of a solve that gave the lists up).  Process-wide counts, for tests and tools. */

@@ -1,6 +1,7 @@
 """The end of every batch of the several-searches-at-once kernel (wide_aug<.., PAR>) by parts, per workgroup.
 Needs a -DCYTO_AUG_FIN_SPLIT build of the library (tools/build_variant.sh split -DCYTO_AUG_FIN_SPLIT), loaded through CYTOHIP_LIB.
-usage: fin_split.py [u20000 u50000 ...] [--reps K] [--par K] [--batches]      (--batches: one line per batch of the last rep)
+usage: fin_split.py [u20000 u50000 ...] [--reps K] [--par K] [--batches] [--doomed]      (--batches: one line per batch of the last rep;
+--doomed: per batch, how long it waited for searches that were then discarded -- last arrival less last committed arrival -- and the sum)
 
 Per batch: the maximum over the workgroups of every part, and the parts of the batch's DEEPEST search (the last workgroup to reach the
 end of its search: everybody else waits for it).  Per solve: the sums of both over the batches, in ms."""
@@ -19,7 +20,7 @@ from tools import instances as I  # noqa: E402
 GOLD = os.path.join(ROOT, "tests", "golden")
 PARTS = ["claim", "wait1", "check", "wait2", "update", "walk", "cost", "reset", "wait3+log", "repair+bar4"]
 WAITS = {"wait1", "wait2", "wait3+log"}
-NTOUCH, SETTLED, HOPS, ARRIVE = 10, 11, 12, 13
+NTOUCH, SETTLED, HOPS, ARRIVE, ABORTED = 10, 11, 12, 13, 14
 
 
 def dump():
@@ -73,6 +74,26 @@ def main():
                   f"settled {int(d[rows, deep, SETTLED].sum())} (largest {int(d[rows, deep, SETTLED].max())}), "
                   f"path hops {int(d[rows, deep, HOPS].sum())} (longest {int(d[rows, deep, HOPS].max())}); "
                   f"all searches: ntouch {int(d[:, :, NTOUCH].sum())} settled {int(d[:, :, SETTLED].sum())}")
+            if "--doomed" in sys.argv:
+                # what a batch waits for searches that are then discarded: the last arrival of all its searches less the last arrival
+                # of a committed one (a committed search has flipped a path: hops > 0).  The sum over the batches is the most that
+                # ending doomed searches early can take off the solve.
+                arr = d[:, :, ARRIVE]
+                com = d[:, :, HOPS] > 0
+                last_all = arr.max(axis=1)
+                last_com = np.where(com, arr, 0).max(axis=1)
+                ok = com.any(axis=1)
+                gap = np.where(ok, last_all - last_com, 0) * 1e-2                           # us
+                # (a library with the early end of doomed searches records which searches it aborted: part 14)
+                ab = d[:, :, ABORTED] > 0 if d.shape[2] > ABORTED else np.zeros(arr.shape, bool)
+                print(f"    aborted searches: {int(ab.sum())} of {int(inf.wide_par_discarded)} discarded")
+                print(f"    doomed: sum over batches of (last arrival - last committed arrival) {gap.sum() * 1e-3:.3f} ms, "
+                      f"largest {gap.max():.1f} us in batch {int(gap.argmax())}, batches with a gap {int((gap > 0).sum())} of {nb}"
+                      + ("" if ok.all() else f"; {int((~ok).sum())} batches without a committed search left out"))
+                if rep == reps - 1:
+                    for b in range(nb):
+                        print(f"    batch {b:4d} committed={int(com[b].sum()):2d} aborted={int(ab[b].sum()):2d} last g={int(deep[b]):2d} "
+                              f"last committed g={int(np.where(com[b], arr[b], 0).argmax()):2d} gap={gap[b]:8.1f} us")
             if "--batches" in sys.argv and rep == reps - 1:
                 for b in range(nb):
                     print(f"    batch {b:4d} deepest g={int(deep[b]):2d} ntouch={int(d[b, deep[b], NTOUCH]):6d} settled={int(d[b, deep[b], SETTLED]):6d} "
