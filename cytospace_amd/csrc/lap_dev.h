@@ -1,5 +1,5 @@
 // lap_dev.h -- device helpers shared by the LAP kernels (lap_jv.hip: the streaming kernels of every float32 solve; lap_chain_f32.hip:
-// the float32 chain solver; lap_f64.hip: the float64 solver; lap_wide.hip: the wide solver; lap_exact.hip: the certificate and the
+// the float32 chain solver; lap_f64.hip: the float64 solver; lap_wide.hip, lap_wide_rr.hip, lap_wide_drv.hip: the wide solver; lap_exact.hip: the certificate and the
 // exact option):
 // the status block of a solve (LapStatus) with its counter and timer indices, order-preserving float keys, DPP wave reductions, the
 // LDS-only barrier, the row-cache constants.
@@ -44,7 +44,7 @@ struct LapStatus {
     int pad1_[2];
     long long wide[WC_N];               // WC_*
     long long timers[WT_N];             // WT_*
-    unsigned char arr[128];             // wide_arr's phase machine (lap_wide.hip: ArrHead)
+    unsigned char arr[128];             // wide_arr's phase machine (lap_wide_rr.hip: ArrHead)
 };
 static_assert(sizeof(LapStatus) == 512, "LapStatus layout");
 static_assert(offsetof(LapStatus, nonfinite) == 0 && offsetof(LapStatus, status) == 4 && offsetof(LapStatus, total) == 8, "LapStatus layout");

@@ -15,7 +15,7 @@
 //       plus a floor that bounds every other column (a certificate while prices only decrease).
 //   colred_partial_append / fused_w / fused_theta / fused_fixup : the first row caches out of the column reduction's own pass.
 // (2) The float32 batch driver (lap_solve_f32_batch) and the C entry points.  The driver hands the problems to one of two solvers:
-//   the wide solver -- what runs by default -- lap_wide.hip, or the chain solver (jv_chain2, jv_aug2, jv_aug_lazy), lap_chain_f32.hip.
+//   the wide solver -- what runs by default -- lap_wide.hip (with lap_wide_rr.hip, lap_wide_drv.hip), or the chain solver (jv_chain2, jv_aug2, jv_aug_lazy), lap_chain_f32.hip.
 // The float64 solver (jv_chain<T, CH>, jv_chain_stream) is lap_f64.hip, the float64 certificate and the exact option lap_exact.hip.
 //
 // Compile with -ffp-contract=off (build.py does): the arithmetic is subtract/compare only,
@@ -375,7 +375,7 @@ __global__ __launch_bounds__(64 * CBW) void build_row_caches_wave(int n, int64_t
             float lo = 0.0f, hi = INFINITY;
             bool okc = false;
             {   // the 35th smallest of the 64 lane minima: 49 +- 5 columns lie below it whatever the distribution (distinct values;
-                //  lap_wide.hip, SC_FLOOR_POS) -- the bisection that follows is for rows with ties
+                //  lap_wide_rr.hip, SC_FLOOR_POS) -- the bisection that follows is for rows with ties
                 float lm = lmin;
 #pragma unroll
                 for (int k = 2; k <= 64; k <<= 1) {
@@ -731,7 +731,7 @@ struct F32Job {
     DevBuf staged, b_fws, b_iws, b_imin, b_pmin, b_parg, b_misc, b_same, b_gid, b_ccol, b_cval;
     DevBuf b_chain[CHAIN_STATE_BUFS];   // the chain solver's own state (lap_chain_f32.hip allocates it)
     DevBuf b_rowmap, b_ulist, b_ufirst;
-    DevBuf b_wide;              // the wide solver's own state (lap_wide.hip allocates it)
+    DevBuf b_wide;              // the wide solver's own state (lap_wide_drv.hip allocates it)
     int nused = 0;
     const float *dcost = nullptr; int64_t dld = 0;
     int h_nonfinite = 0, h_ngroups = 0;

@@ -1,5 +1,5 @@
-// lap_wide.h -- the interface between the float32 driver (lap_jv.hip) and the wide solver (lap_wide.hip); the row-cache build and the
-// description of a problem (SolveJob) also serve the float32 chain solver (lap_chain_f32.h).
+// lap_wide.h -- the interface between the float32 driver (lap_jv.hip) and the wide solver (lap_wide_drv.hip: the driver;
+// lap_wide.hip: the searches; lap_wide_rr.hip: the row reduction); the row-cache build and the description of a problem (SolveJob) also serve the float32 chain solver (lap_chain_f32.h).
 #pragma once
 #include "cyto_common.h"
 #include "lap_dev.h"
@@ -21,13 +21,13 @@ int build_caches(const CachePlan &cp, int n, int64_t ld, const float *cost, cons
                  float *cache_val, const int32_t *same, hipStream_t stream, const int32_t *rowlist = nullptr, int count = 0);
 
 // One problem of a batch as the float32 driver has set it up (lap_jv.hip: F32Job, private to it, after the column reduction), for
-// either solver.  Device memory.  (The slots of fws / iws are named as the wide solver uses them; the chain solver's use: Chain2Args and
+// either solver.  Device memory.  (The slots of fws / iws are named as the wide solver uses them -- lap_wide_dev.h: FWS_*, IWS_* -- ; the chain solver's use: Chain2Args and
 // LazyArgs, lap_chain_f32.hip.  first_rows / first_count: the wide solver only.)
 struct SolveJob {
     const float *cost; int64_t ld;
     const int32_t *rowmap;              // [n] LAP row i reads stored row rowmap[i], or null
-    float *fws;                         // [6n + 16] v | u | - | cassign | label (2n)
-    int32_t *iws;                       // [10n + 16] rowsol | colsol | matches | freerows | act0 | act1 | touched | slot_j | bid (2n)
+    float *fws;                         // [6n + 16] FWS_V | FWS_U | - | FWS_CASSIGN | FWS_LABEL (2n)
+    int32_t *iws;                       // [10n + 16] IWS_ROWSOL | _COLSOL | _MATCHES | _FREEROWS | _ACT0 | _ACT1 | _TOUCHED | _SLOT_J | _BID (2n)
     uint32_t *cache_col; float *cache_val;      // [n][64] row caches
     char *misc;                         // the status block (lap_dev.h: LapStatus)
     const int32_t *same;                // [n] 1 = the row equals the row before it (runs of identical rows), or null

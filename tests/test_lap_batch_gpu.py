@@ -10,7 +10,7 @@ instance (the cache below is keyed by the instance's name; groups repeat instanc
 reference; (f) and (g) use device results only where no CPU value exists (the context's own cost rows, the float64 certificate).
 
 Group sizes and the constant of the driver each one is there for:
-  n (a):  1, 2, 3, 5      want_groups = n >= 2, `if (n >= 2 && !resume)`: the degenerate launches (lap_jv.hip, lap_wide.hip)
+  n (a):  1, 2, 3, 5      want_groups = n >= 2, `if (n >= 2 && !resume)`: the degenerate launches (lap_jv.hip, lap_wide_rr.hip)
           63, 64, 65      KC = 63 cached columns per row / one wave: the row cache holds the whole row, exactly, or misses one column
           300, 1000       the plain LDS-resident sizes (jv_chain2<2 / 5, true>)
           2100, 4200      the n >= 2048 and n >= 4096 rules of wide_solve_batch (whole-chip first rounds, long-list rounds in wide_arr)

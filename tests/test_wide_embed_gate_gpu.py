@@ -1,4 +1,4 @@
-"""The gate of the embedded form, taken on the device (lap_wide.hip: wide_solve_batch enqueues wide_aug<.., EMB> and its plain twin
+"""The gate of the embedded form, taken on the device (lap_wide_drv.hip: wide_solve_batch enqueues wide_aug<.., EMB> and its plain twin
 back to back behind the build of the inverse lists; each reads the longest list and the one whose turn it is not returns at once;
 which one ran comes back in the status block and moves cyto_wide_embedded_solves()).
 

@@ -4,12 +4,12 @@
 # e.g.  tools/build_variant.sh coop0 -DCYTO_COOP_MIN_N=0      (tools/run/r06r.sh, r06z.sh)
 #       tools/build_variant.sh stop128 -DWIDE_STOP_CAP=128
 #       VARIANT_SRCS=lap_jv.hip tools/build_variant.sh probe1 -DCYTO_COLRED_PROBE=1
-# Only the sources in VARIANT_SRCS (default: lap_wide.hip) are recompiled with the flags; the other objects come from the last
+# Only the sources in VARIANT_SRCS (default: the wide solver's three, lap_wide.hip lap_wide_rr.hip lap_wide_drv.hip) are recompiled with the flags; the other objects come from the last
 # `python -m cytospace_amd.build` (VARIANT_NO_BASE=1: do not run it again first -- several variants built side by side).
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 name=$1; shift
-srcs=${VARIANT_SRCS:-lap_wide.hip}
+srcs=${VARIANT_SRCS:-lap_wide.hip lap_wide_rr.hip lap_wide_drv.hip}
 [ -n "$VARIANT_NO_BASE" ] || python -m cytospace_amd.build > /dev/null
 vobjs=""
 for s in $srcs; do
