@@ -234,6 +234,21 @@ def lib():
         L.cyto_mtx_read.restype = ctypes.c_int
         L.cyto_mtx_parse_entries.argtypes = [vp, i64, vp, i32, i64, i64, vp, vp, vp, vp, vp]
         L.cyto_mtx_parse_entries.restype = ctypes.c_int
+        L.cyto_table_values.argtypes = [vp, ctypes.POINTER(vp), i64p]
+        L.cyto_table_values.restype = ctypes.c_int
+        L.cyto_table_fetch_labels.argtypes = [vp, vp, vp, dp]
+        L.cyto_table_fetch_labels.restype = ctypes.c_int
+        L.cyto_downsample_dev.argtypes = L.cyto_downsample.argtypes
+        L.cyto_downsample_dev.restype = ctypes.c_int
+        L.cyto_mtx_write_dev.argtypes = L.cyto_mtx_write_ex.argtypes
+        L.cyto_mtx_write_dev.restype = ctypes.c_int
+        view = [i64, i64, vp, i64, i32, vp, i64, vp, i64]          # G, C, src_dev, ld_src, src_dtype, rows, Gs, cols, Cs
+        L.cyto_select.argtypes = view + [vp, i64, i32, i64p, i32, vp]
+        L.cyto_select.restype = ctypes.c_int
+        L.cyto_value_range.argtypes = view + [dp, dp, i64p, i64p, i64p, i64p, i64p, i32, vp]
+        L.cyto_value_range.restype = ctypes.c_int
+        L.cyto_select_check.argtypes = [vp, i32, i64, i32, vp]
+        L.cyto_select_check.restype = ctypes.c_int
         L.cyto_comm_unique_id.argtypes = [ctypes.c_char_p]
         L.cyto_comm_init.argtypes = [ctypes.c_char_p, i32, i32, i32, ctypes.POINTER(vp)]
         L.cyto_comm_init_local.argtypes = [i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(vp)]

@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libcytohip.so")
 SOURCES = ["core.hip", "lap_jv.hip", "lap_chain_f32.hip", "lap_f64.hip", "lap_exact.hip", "lap_wide.hip", "lap_wide_rr.hip", "lap_wide_drv.hip", "cost.hip",
-           "batch.hip", "comm.hip", "downsample.hip", "table.hip", "mtx.hip", "mtx_read.hip", "csv.hip"]
+           "batch.hip", "comm.hip", "downsample.hip", "table.hip", "mtx.hip", "mtx_read.hip", "csv.hip", "resident.hip"]
 # -ffp-contract=off: the JV kernels must evaluate exactly the subtract/compare sequence of the
 # oracle (no FMA contraction, no re-association).  MFMA use in the cost kernels is explicit.
 # (CYTO_EXTRA_FLAGS: developer builds, e.g. -DWIDE_STOP_CAP=128 for tools/exp -- use with --force and rebuild afterwards)

@@ -133,8 +133,10 @@ def _table_head(header, first, sep, C):
     return head
 
 
-def _table_on_device(file_path, device_id, info):
-    """read_file_device's device path: the DataFrame, or None (info["reason"] says why) for a file outside its grammar."""
+def _table_on_device(file_path, device_id, info, resident=False):
+    """read_file_device's device path: the DataFrame, or None (info["reason"] says why) for a file outside its grammar.  resident:
+    a resident.DeviceFrame over the parsed values where a frame can stand for the table (only the labels are fetched and the
+    handle stays with the frame), else the DataFrame as before (info["resident_reason"] says why)."""
     import time
 
     def refuse(kind, line=0, byte=0):
@@ -178,6 +180,25 @@ def _table_on_device(file_path, device_id, info):
     if st == 7:                                                              # CYTO_ERR_UNSUPPORTED
         return refuse(_TABLE_REFUSALS.get(why[0], str(why[0])), why[1], why[2])
     _lib.check(st)
+    if resident:
+        from . import resident as _resident
+        frame = None
+        try:
+            G, C, nlab = shape
+            is_float = np.empty(C, np.int8)
+            labels = np.empty(nlab, np.uint8)
+            _lib.check(L.cyto_table_fetch_labels(h, is_float.ctypes.data, labels.ctypes.data, ctypes.byref(ms_dl)))
+            info["download_s"] = ms_dl.value / 1e3
+            frame = _resident.from_table(h, G, head, is_float, labels, sep, device_id, info)
+        except BaseException:
+            L.cyto_table_free(h)
+            raise
+        if frame is not None:
+            info["resident"] = True
+            return frame
+        if "reason" in info:                             # (row labels outside the grammar: pandas reads the file)
+            L.cyto_table_free(h)
+            return None
     try:
         G, C, nlab = shape
         values = np.empty((G, C), np.int64)
@@ -224,7 +245,7 @@ def _table_frame(head, values, is_float, labels, sep, info):
     return df
 
 
-def read_file_device(file_path, device_id=0, return_info=False):
+def read_file_device(file_path, device_id=0, return_info=False, resident=False):
     """read_file(file_path, keep_sparse=False) for a dense delimited text table (.csv: ','; otherwise tab), parsed on the GPU
     (C ABI: cyto_table_read / cyto_table_fetch; csrc/table.hip).  The result is equal to read_file's: index, columns (pandas'
     header parse, duplicates mangled), every column's dtype (int64 or float64) and every value bit for bit (pandas' own decimal
@@ -235,11 +256,15 @@ def read_file_device(file_path, device_id=0, return_info=False):
     return_info: also return a dict -- "path" ("device" or "pandas"), for a fallback "reason" {"kind", "line", "byte"}, and the
     phase times in seconds: header_s (pandas' parse of the header), file_read_s, upload_s (what the upload added to the reads),
     kernels_s, device_setup_s (the rest of the device call: allocations, pinned buffers, their release), download_s, free_s,
-    dataframe_s (the row labels' parse and the DataFrame), total_s."""
+    dataframe_s (the row labels' parse and the DataFrame), total_s.
+
+    resident=True: a table the device path takes whose columns are all int64 or all float64, with unique column labels, comes
+    back as a resident.DeviceFrame -- the values stay in HBM, only the labels are fetched, `.to_frame()` is the DataFrame above.
+    Every other input gives the DataFrame as before.  info["resident"] says which (for a DataFrame, info["resident_reason"] why)."""
     import time
     t = time.perf_counter()
-    info = {"path": "device"}
-    df = _table_on_device(file_path, device_id, info)
+    info = {"path": "device", "resident": False}
+    df = _table_on_device(file_path, device_id, info, resident)
     if df is None:
         info["path"] = "pandas"
         df = read_file(file_path, keep_sparse=False)
@@ -443,7 +468,9 @@ def downsample_device(data_df, target_count, device_id=0, dtype=np.int64, return
     target_count).  return_words: also return the number of raw MT19937 words consumed.  Raises TypeError for a non-integer matrix (np.repeat refuses it) and ValueError, before any draw,
     for a negative count in a cell that is downsampled or a cell total above 2^32."""
     import pandas as pd
-    x = data_df.to_numpy()
+    from . import resident as _resident
+    frame = data_df if _resident.is_frame(data_df) else None
+    x = np.empty((0, 0), frame.dtype) if frame is not None else data_df.to_numpy()
     if x.dtype.kind not in "biu" or x.dtype == np.uint64:
         raise TypeError(f"Cannot downsample counts of dtype {x.dtype}: an integer count matrix is required")
     dtype = np.dtype(dtype)
@@ -456,10 +483,16 @@ def downsample_device(data_df, target_count, device_id=0, dtype=np.int64, return
         raise ValueError("dtype=np.uint16 needs target_count < 65536")
     if target > 2**31 - 1:
         raise ValueError("target_count must be below 2^31")
-    G, C = x.shape
+    G, C = data_df.shape
+    if frame is not None and (G == 0 or C == 0):
+        x = frame.to_numpy()
     if G == 0 or C == 0:
         df = pd.DataFrame(x.astype(dtype), index=data_df.index, columns=data_df.columns)
+        if frame is not None:
+            df = _resident.DeviceFrame.from_frame(df.astype(dtype), device_id)
         return (df, 0) if return_words else df
+    if frame is not None:
+        return _downsample_frame(frame, target, device_id, dtype, return_words)
     if x.dtype in _DS_WIDEN:
         x = x.astype(_DS_WIDEN[x.dtype])
     x = np.ascontiguousarray(x)
@@ -480,6 +513,37 @@ def downsample_device(data_df, target_count, device_id=0, dtype=np.int64, return
     np.random.set_state(("MT19937", key, pos.value, state[3], state[4]))
     df = pd.DataFrame(out, index=data_df.index, columns=data_df.columns)
     return (df, words.value) if return_words else df
+
+
+def _downsample_frame(frame, target, device_id, dtype, return_words):
+    """downsample_device for a resident.DeviceFrame: the view is materialised to int64 on the device, cyto_downsample_dev writes
+    a second buffer, and the result is the frame over it; only the cells' totals and the generator's state cross PCIe."""
+    from . import resident as _resident
+    G, C = frame.shape
+    state = np.random.get_state()
+    if state[0] != "MT19937":
+        raise ValueError("numpy's global generator is not MT19937")
+    key = np.array(state[1], dtype=np.uint32)
+    pos = ctypes.c_int32(int(state[2]))
+    words = ctypes.c_int64()
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    x = frame.materialize(np.int64)
+    out = _lib.DeviceBuffer(G * C * dtype.itemsize, device_id)
+    try:
+        st = _lib.lib().cyto_downsample_dev(G, C, x.ptr, x.ld, _lib.CYTO_DTYPE_I64, out.ptr, C, 5 if dtype == np.int64 else 2, target,
+                                            key.ctypes.data_as(u32p), ctypes.byref(pos), ctypes.byref(words), device_id)
+        if st == 1:
+            raise ValueError("cannot downsample: a cell with more than target_count transcripts holds a negative count or more than "
+                             "2^32 transcripts" + (" (or, with dtype=np.uint16, some count is negative)" if dtype == np.uint16 else ""))
+        _lib.check(st)
+    except BaseException:
+        out.free()
+        raise
+    finally:
+        x.close()
+    np.random.set_state(("MT19937", key, pos.value, state[3], state[4]))
+    res = _resident.DeviceFrame(out, (G, C), C, dtype, frame.index, frame.columns, device_id=device_id, stats=frame.stats)
+    return (res, words.value) if return_words else res
 
 
 # upload codes of cyto_placeholders; other dtypes are widened on the host first (to what numpy's float64 assignment sees anyway)

@@ -889,8 +889,13 @@ int cyto_cost_metric(int metric, int Gpad, int S, int C, const float *zst, int64
 // JV solve on the device, mapped_spot[c] = spot of the LAP row given to cell c.
 // sc: G x C, st: G x S (host, row-major, float64 like the reference's arrays).  sum(slots) must be C.
 // The 1e-16 perturbation of cytospace.py:325-327 is not applied: it is a no-op in float32.
+// sc_dev / st_dev: the matrix is already on the device, with leading dimension ldsc / ldst (a host matrix has ld == its columns).
 static int assign_metric_impl(int metric, int G, int C, int S, const void *sc, int sc_dt, const void *st, int st_dt, const int64_t *slots,
-                              int already_normalized, int64_t *mapped_spot, double *total_cost, cyto_assign_info *info, int device_id) {
+                              int already_normalized, int64_t *mapped_spot, double *total_cost, cyto_assign_info *info, int device_id,
+                              int64_t ldsc = 0, int sc_dev = 0, int64_t ldst = 0, int st_dev = 0) {
+    if (!sc_dev) ldsc = C;
+    if (!st_dev) ldst = S;
+    if (ldsc < C || ldst < S) return CYTO_ERR_BAD_ARG;
     if (metric < CYTO_METRIC_PEARSON || metric > CYTO_METRIC_EUCLIDEAN || !dtype_ok(sc_dt) || !dtype_ok(st_dt)) return CYTO_ERR_BAD_ARG;
     const int transform = metric == CYTO_METRIC_PEARSON ? CYTO_TRANSFORM_STANDARDIZE
                         : metric == CYTO_METRIC_SPEARMAN ? CYTO_TRANSFORM_RANK : CYTO_TRANSFORM_RAW;
@@ -923,7 +928,7 @@ static int assign_metric_impl(int metric, int G, int C, int S, const void *sc, i
         (rc = cost.alloc((size_t)S * ldc * 4, stream)))
         return rc;
     CYTO_HIP(hipEventRecord(e0, stream));
-    if ((rc = cyto_transform(transform, G, S, st, S, st_dt, 0, already_normalized, zst.as<float>(), ldzst, Gpad, device_id, stream))) return rc;
+    if ((rc = cyto_transform(transform, G, S, st, ldst, st_dt, st_dev, already_normalized, zst.as<float>(), ldzst, Gpad, device_id, stream))) return rc;
     float ms_std = 0;
     double ms_gemm = 0;
     constexpr int WBLK = 8192;                            // cells per block: 64 column tiles x 40 row tiles at c3 = five full rounds
@@ -938,7 +943,7 @@ static int assign_metric_impl(int metric, int G, int C, int S, const void *sc, i
         if ((rc = gcomp.acquire())) return rc;
         const size_t esz = dtype_size(sc_dt);
         DevBuf dx;
-        if ((rc = dx.alloc((size_t)G * WBLK * esz, stream))) return rc;
+        if (!sc_dev && (rc = dx.alloc((size_t)G * WBLK * esz, stream))) return rc;
         // (only the padding of the operand is cleared -- the columns beyond C, the genes beyond G: the transforms write every element of
         //  the G x C block themselves, and a memset of the whole 4-GB buffer was another pass in front of the first block)
         if (ldzsc > C) CYTO_HIP(hipMemset2DAsync(zsc.as<float>() + C, (size_t)ldzsc * sizeof(float), 0, (size_t)(ldzsc - C) * sizeof(float), (size_t)G, stream));
@@ -958,8 +963,12 @@ static int assign_metric_impl(int metric, int G, int C, int S, const void *sc, i
         for (int b = 0; b < nblocks; b++) {
             const int c0 = bstart[(size_t)b], w = bstart[(size_t)b + 1] - c0;
             const char *src = reinterpret_cast<const char *>(sc) + (size_t)c0 * esz;
-            CYTO_HIP(hipMemcpy2DAsync(dx.p, (size_t)w * esz, src, (size_t)C * esz, (size_t)w * esz, G, hipMemcpyHostToDevice, stream));
-            rc = standardize_any(sc_dt, G, w, dx.p, w, already_normalized, zsc.as<float>() + c0, ldzsc, nullptr, 0, stream, transform);
+            if (sc_dev) {                                 // a resident matrix: the block's columns are transformed where they lie
+                rc = standardize_any(sc_dt, G, w, src, ldsc, already_normalized, zsc.as<float>() + c0, ldzsc, nullptr, 0, stream, transform);
+            } else {
+                CYTO_HIP(hipMemcpy2DAsync(dx.p, (size_t)w * esz, src, (size_t)C * esz, (size_t)w * esz, G, hipMemcpyHostToDevice, stream));
+                rc = standardize_any(sc_dt, G, w, dx.p, w, already_normalized, zsc.as<float>() + c0, ldzsc, nullptr, 0, stream, transform);
+            }
             if (rc) return rc;                            // (standardize_dev has waited for its kernels: block b's operand is complete)
             CYTO_HIP(hipEventRecord(evs[2 * b], gcomp.s));
             gemm_unique_rows_async(Gpad, S, w, zst.as<float>(), ldzst, zsc.as<float>() + c0, ldzsc, nullptr, cost.as<float>() + c0, ldc, gcomp.s);
@@ -972,7 +981,7 @@ static int assign_metric_impl(int metric, int G, int C, int S, const void *sc, i
         (void)hipEventElapsedTime(&ms_std, e0, e1);     // upload + transforms; the contractions of all blocks but the last ran inside it
         for (int b = 0; b < nblocks; b++) { float ms = 0; (void)hipEventElapsedTime(&ms, evs[2 * b], evs[2 * b + 1]); ms_gemm += ms; }
     } else {
-        if ((rc = cyto_transform(transform, G, C, sc, C, sc_dt, 0, already_normalized, zsc.as<float>(), ldzsc, Gpad, device_id, stream))) return rc;
+        if ((rc = cyto_transform(transform, G, C, sc, ldsc, sc_dt, sc_dev, already_normalized, zsc.as<float>(), ldzsc, Gpad, device_id, stream))) return rc;
         CYTO_HIP(hipEventRecord(e1, stream));
         CYTO_HIP(hipEventSynchronize(e1));
         (void)hipEventElapsedTime(&ms_std, e0, e1);
@@ -1007,12 +1016,13 @@ int cyto_assign_metric_typed(int metric, int G, int C, int S, const void *sc, co
     return assign_metric_impl(metric, G, C, S, sc, x_is_f64, st, x_is_f64, slots, already_normalized, mapped_spot, total_cost, info, device_id);
 }
 
-// the same with a dtype per matrix (host matrices, row-major, ld == columns): counts as uint8 / uint16 where they fit
+// the same with a dtype per matrix (row-major; a host matrix has ld == columns, a device matrix any ld >= columns and is read where it
+// lies): counts as uint8 / uint16 where they fit
 int cyto_assign_metric_ex(int metric, int G, const cyto_matrix *sc, int C, const cyto_matrix *st, int S, const int64_t *slots,
                           int already_normalized, int64_t *mapped_spot, double *total_cost, cyto_assign_info *info, int device_id) {
-    if (!sc || !st || sc->on_device || st->on_device || sc->ld != C || st->ld != S) return CYTO_ERR_BAD_ARG;
+    if (!sc || !st || (sc->on_device ? sc->ld < C : sc->ld != C) || (st->on_device ? st->ld < S : st->ld != S)) return CYTO_ERR_BAD_ARG;
     return assign_metric_impl(metric, G, C, S, sc->data, sc->is_f64, st->data, st->is_f64, slots, already_normalized, mapped_spot, total_cost, info,
-                              device_id);
+                              device_id, sc->ld, sc->on_device != 0, st->ld, st->on_device != 0);
 }
 
 // ---- multi-chunk seam (apply_linear_assignment, cytospace/cytospace.py:354-469): the two expression matrices are

@@ -349,8 +349,11 @@ int load_state(MtState &h, const uint32_t *key, const int32_t *pos) {
 
 }  // namespace
 
-int cyto_downsample(int G, int C, const void *x, int64_t ldx, int x_dtype, void *out, int64_t ldo, int out_dtype, int target,
-                    uint32_t *key, int32_t *pos, int64_t *words_out, int device_id) {
+namespace {
+// cyto_downsample (on_device = false: x and out are host matrices, staged through dx / dout) and cyto_downsample_dev (true: the
+// kernels read x and write out where they lie, with the caller's leading dimensions)
+int downsample_impl(int G, int C, const void *x, int64_t ldx, int x_dtype, void *out, int64_t ldo, int out_dtype, int target,
+                    uint32_t *key, int32_t *pos, int64_t *words_out, int device_id, bool on_device) {
     if (G <= 0 || C <= 0 || !x || !out || ldx < C || ldo < C || target < 0 || !key || !pos) return CYTO_ERR_BAD_ARG;
     const size_t in_sz = dtype_size(x_dtype);
     if (!in_sz || (out_dtype != CYTO_DTYPE_I64 && out_dtype != CYTO_DTYPE_U16)) return CYTO_ERR_BAD_ARG;
@@ -367,17 +370,23 @@ int cyto_downsample(int G, int C, const void *x, int64_t ldx, int x_dtype, void 
     Mem dx, dout, dtot, dneg, dflag, dstate, dcells, drng, drbuf;
     StreamGuard sa, sb;                                  // sa: upload, totals, copies, stage 2; sb: stage 1
     if ((rc = sa.acquire()) || (rc = sb.acquire())) return rc;
-    if ((rc = dx.alloc((size_t)G * C * in_sz)) || (rc = dout.alloc((size_t)G * C * out_sz)) || (rc = dtot.alloc((size_t)C * 8)) ||
-        (rc = dneg.alloc((size_t)C * 4)) || (rc = dflag.alloc((size_t)C * 4)) || (rc = dstate.alloc(sizeof(MtState))))
+    if ((rc = dtot.alloc((size_t)C * 8)) || (rc = dneg.alloc((size_t)C * 4)) || (rc = dflag.alloc((size_t)C * 4)) ||
+        (rc = dstate.alloc(sizeof(MtState))))
         return rc;
-    CYTO_HIP(hipMemcpy2DAsync(dx.p, (size_t)C * in_sz, x, (size_t)ldx * in_sz, (size_t)C * in_sz, (size_t)G, hipMemcpyHostToDevice, sa.s));
+    if (!on_device) {
+        if ((rc = dx.alloc((size_t)G * C * in_sz)) || (rc = dout.alloc((size_t)G * C * out_sz))) return rc;
+        CYTO_HIP(hipMemcpy2DAsync(dx.p, (size_t)C * in_sz, x, (size_t)ldx * in_sz, (size_t)C * in_sz, (size_t)G, hipMemcpyHostToDevice, sa.s));
+    }
+    const void *xp = on_device ? x : dx.p;                // the matrices as the kernels see them
+    void *op = on_device ? out : dout.p;
+    const int64_t xl = on_device ? ldx : C, ol = on_device ? ldo : C;
     CYTO_HIP(hipMemsetAsync(dtot.p, 0, (size_t)C * 8, sa.s));
     CYTO_HIP(hipMemsetAsync(dneg.p, 0, (size_t)C * 4, sa.s));
     switch (x_dtype) {
-        case CYTO_DTYPE_U8: rc = launch_totals<uint8_t>(dx.p, C, G, C, dtot.as<unsigned long long>(), dneg.as<int>(), sa.s); break;
-        case CYTO_DTYPE_U16: rc = launch_totals<uint16_t>(dx.p, C, G, C, dtot.as<unsigned long long>(), dneg.as<int>(), sa.s); break;
-        case CYTO_DTYPE_I32: rc = launch_totals<int32_t>(dx.p, C, G, C, dtot.as<unsigned long long>(), dneg.as<int>(), sa.s); break;
-        default: rc = launch_totals<int64_t>(dx.p, C, G, C, dtot.as<unsigned long long>(), dneg.as<int>(), sa.s); break;
+        case CYTO_DTYPE_U8: rc = launch_totals<uint8_t>(xp, xl, G, C, dtot.as<unsigned long long>(), dneg.as<int>(), sa.s); break;
+        case CYTO_DTYPE_U16: rc = launch_totals<uint16_t>(xp, xl, G, C, dtot.as<unsigned long long>(), dneg.as<int>(), sa.s); break;
+        case CYTO_DTYPE_I32: rc = launch_totals<int32_t>(xp, xl, G, C, dtot.as<unsigned long long>(), dneg.as<int>(), sa.s); break;
+        default: rc = launch_totals<int64_t>(xp, xl, G, C, dtot.as<unsigned long long>(), dneg.as<int>(), sa.s); break;
     }
     if (rc) return rc;
     CYTO_HIP(hipMemcpyAsync(tot.data(), dtot.p, (size_t)C * 8, hipMemcpyDeviceToHost, sa.s));
@@ -398,7 +407,7 @@ int cyto_downsample(int G, int C, const void *x, int64_t ldx, int x_dtype, void 
     if (any_neg && out_dtype == CYTO_DTYPE_U16) return CYTO_ERR_BAD_ARG;       // a kept negative count has no uint16 value
     const int nd = (int)cells.size();
     CYTO_HIP(hipMemcpyAsync(dflag.p, flag.data(), (size_t)C * 4, hipMemcpyHostToDevice, sa.s));
-    if ((rc = dispatch(x_dtype, out_dtype, dx.p, C, G, C, dflag.as<int>(), dout.p, C, sa.s, 0, nullptr, nullptr, 0, true))) return rc;
+    if ((rc = dispatch(x_dtype, out_dtype, xp, xl, G, C, dflag.as<int>(), op, ol, sa.s, 0, nullptr, nullptr, 0, true))) return rc;
 
     if (nd > 0) {
         const int per = (int)std::max<size_t>(1, std::min<size_t>((size_t)nd, target ? rbuf_bytes() / ((size_t)target * 4) : (size_t)nd));
@@ -423,20 +432,33 @@ int cyto_downsample(int G, int C, const void *x, int64_t ldx, int x_dtype, void 
             }
             CYTO_HIP(hipEventRecord(ev[1 + buf], sb.s));
             CYTO_HIP(hipStreamWaitEvent(sa.s, ev[1 + buf], 0));
-            if ((rc = dispatch(x_dtype, out_dtype, dx.p, C, G, C, nullptr, dout.p, C, sa.s, n, dcells.as<int>() + d0, rb, target, false)))
+            if ((rc = dispatch(x_dtype, out_dtype, xp, xl, G, C, nullptr, op, ol, sa.s, n, dcells.as<int>() + d0, rb, target, false)))
                 return rc;
             CYTO_HIP(hipEventRecord(ev[3 + buf], sa.s));
         }
         CYTO_HIP(hipStreamSynchronize(sb.s));
         CYTO_HIP(hipMemcpyAsync(&hs, dstate.p, sizeof hs, hipMemcpyDeviceToHost, sa.s));
     }
-    CYTO_HIP(hipMemcpy2DAsync(out, (size_t)ldo * out_sz, dout.p, (size_t)C * out_sz, (size_t)C * out_sz, (size_t)G, hipMemcpyDeviceToHost,
-                              sa.s));
+    if (!on_device)
+        CYTO_HIP(hipMemcpy2DAsync(out, (size_t)ldo * out_sz, dout.p, (size_t)C * out_sz, (size_t)C * out_sz, (size_t)G, hipMemcpyDeviceToHost,
+                                  sa.s));
     CYTO_HIP(hipStreamSynchronize(sa.s));
     memcpy(key, hs.key, sizeof hs.key);
     *pos = (int32_t)hs.pos;
     if (words_out) *words_out = (int64_t)hs.words;
     return CYTO_OK;
+}
+}  // namespace
+
+int cyto_downsample(int G, int C, const void *x, int64_t ldx, int x_dtype, void *out, int64_t ldo, int out_dtype, int target,
+                    uint32_t *key, int32_t *pos, int64_t *words_out, int device_id) {
+    return downsample_impl(G, C, x, ldx, x_dtype, out, ldo, out_dtype, target, key, pos, words_out, device_id, false);
+}
+
+int cyto_downsample_dev(int G, int C, const void *x_dev, int64_t ldx, int x_dtype, void *out_dev, int64_t ldo, int out_dtype, int target,
+                        uint32_t *key, int32_t *pos, int64_t *words_out, int device_id) {
+    if (x_dev == out_dev) return CYTO_ERR_BAD_ARG;
+    return downsample_impl(G, C, x_dev, ldx, x_dtype, out_dev, ldo, out_dtype, target, key, pos, words_out, device_id, true);
 }
 
 int cyto_placeholders(int G, int n, const void *own, int64_t ld_own, int own_dtype, int64_t short_count, double *out, int64_t ldo,

@@ -283,8 +283,10 @@ int cyto_mtx_write(const char *path, int64_t G, int64_t N, const void *x, int64_
     return cyto_mtx_write_ex(path, G, N, x, ldx, x_dtype, cols, C, block_bytes, device_id, 0, info);
 }
 
-int cyto_mtx_write_ex(const char *path, int64_t G, int64_t N, const void *x, int64_t ldx, int x_dtype, const int64_t *cols, int64_t C,
-                      int64_t block_bytes, int device_id, int flags, cyto_mtx_info *info) {
+namespace {
+// cyto_mtx_write_ex (on_device = false: x is a host matrix, uploaded whole) and cyto_mtx_write_dev (true: the kernels read x where it lies)
+int mtx_write_impl(const char *path, int64_t G, int64_t N, const void *x, int64_t ldx, int x_dtype, const int64_t *cols, int64_t C,
+                   int64_t block_bytes, int device_id, int flags, cyto_mtx_info *info, bool on_device) {
     const size_t es = dtype_size(x_dtype);
     const bool frac = (flags & CYTO_TEXT_FRACTIONS) != 0;
     if ((flags & ~CYTO_TEXT_FRACTIONS) || !path || !x || !cols || !info || es == 0 || G <= 0 || N <= 0 || C <= 0 || ldx < N || block_bytes < 0 || G > 0x7fffffffll ||
@@ -313,14 +315,15 @@ int cyto_mtx_write_ex(const char *path, int64_t G, int64_t N, const void *x, int
     OutFile f;
     StreamGuard sg, sc;
     if ((rc = sg.acquire()) || (rc = sc.acquire()) || (rc = ev.create())) return rc;
-    if ((rc = dx.alloc((size_t)(G * ldx) * es)) || (rc = dcols.alloc((size_t)C * 8)) || (rc = seg_off.alloc((size_t)(G * nseg) * 8)) ||
+    if ((!on_device && (rc = dx.alloc((size_t)(G * ldx) * es))) || (rc = dcols.alloc((size_t)C * 8)) || (rc = seg_off.alloc((size_t)(G * nseg) * 8)) ||
         (rc = row_bytes.alloc((size_t)G * 8)) || (rc = row_nnz.alloc((size_t)G * 8)) || (rc = row_off.alloc((size_t)(G + 1) * 8)) ||
         (rc = scal.alloc(16)))
         return rc;
 
     // (1) the matrix and the column list
     const auto t0 = std::chrono::steady_clock::now();
-    CYTO_HIP(hipMemcpyAsync(dx.p, x, (size_t)(G * ldx) * es, hipMemcpyHostToDevice, sg.s));
+    if (!on_device) CYTO_HIP(hipMemcpyAsync(dx.p, x, (size_t)(G * ldx) * es, hipMemcpyHostToDevice, sg.s));
+    const void *xp = on_device ? x : dx.p;              // the matrix as the kernels see it
     CYTO_HIP(hipMemcpyAsync(dcols.p, cols, (size_t)C * 8, hipMemcpyHostToDevice, sg.s));
     CYTO_HIP(hipStreamSynchronize(sg.s));
     info->ms_upload = ms_since(t0);
@@ -328,7 +331,7 @@ int cyto_mtx_write_ex(const char *path, int64_t G, int64_t N, const void *x, int
     // (2) counts, offsets, the values outside the grammar
     const auto t1 = std::chrono::steady_clock::now();
     CYTO_HIP(hipMemsetAsync(scal.p, 0, 16, sg.s));
-    MTX_DISPATCH(x_dtype, frac, hipLaunchKernelGGL((mtx_count<T, FRAC>), dim3((unsigned)G), dim3(WG), 0, sg.s, dx.as<T>(), ldx, dcols.as<int64_t>(), C,
+    MTX_DISPATCH(x_dtype, frac, hipLaunchKernelGGL((mtx_count<T, FRAC>), dim3((unsigned)G), dim3(WG), 0, sg.s, (const T *)xp, ldx, dcols.as<int64_t>(), C,
                                              nseg, seg_off.as<int64_t>(), row_bytes.as<int64_t>(), row_nnz.as<int64_t>(),
                                              scal.as<int>() + 2));
     CYTO_HIP(hipGetLastError());
@@ -404,7 +407,7 @@ int cyto_mtx_write_ex(const char *path, int64_t G, int64_t N, const void *x, int
             CYTO_HIP(hipEventRecord(ev[b], sg.s));
             for (int64_t r0 = ga; r0 < gb; r0 += max_rows) {
                 const int64_t rows = std::min(max_rows, gb - r0);
-                MTX_DISPATCH(x_dtype, frac, hipLaunchKernelGGL((mtx_format<T, FRAC>), dim3((unsigned)(rows * nseg)), dim3(WG), 0, sg.s, dx.as<T>(), ldx,
+                MTX_DISPATCH(x_dtype, frac, hipLaunchKernelGGL((mtx_format<T, FRAC>), dim3((unsigned)(rows * nseg)), dim3(WG), 0, sg.s, (const T *)xp, ldx,
                                                          dcols.as<int64_t>(), C, nseg, r0, row_off.as<int64_t>(), seg_off.as<int64_t>(),
                                                          hoff[(size_t)ga], dbuf[b].as<uint8_t>()));
                 CYTO_HIP(hipGetLastError());
@@ -420,6 +423,17 @@ int cyto_mtx_write_ex(const char *path, int64_t G, int64_t N, const void *x, int
     if ((rc = finish(nb - 1))) return rc;
     f.keep = true;
     return CYTO_OK;
+}
+}  // namespace
+
+int cyto_mtx_write_ex(const char *path, int64_t G, int64_t N, const void *x, int64_t ldx, int x_dtype, const int64_t *cols, int64_t C,
+                      int64_t block_bytes, int device_id, int flags, cyto_mtx_info *info) {
+    return mtx_write_impl(path, G, N, x, ldx, x_dtype, cols, C, block_bytes, device_id, flags, info, false);
+}
+
+int cyto_mtx_write_dev(const char *path, int64_t G, int64_t N, const void *x_dev, int64_t ldx, int x_dtype, const int64_t *cols, int64_t C,
+                       int64_t block_bytes, int device_id, int flags, cyto_mtx_info *info) {
+    return mtx_write_impl(path, G, N, x_dev, ldx, x_dtype, cols, C, block_bytes, device_id, flags, info, true);
 }
 
 int cyto_mtx_format_entries(const int64_t *rows, const int64_t *cols, const void *values, int dtype, int64_t n, char *out,

@@ -444,6 +444,26 @@ int cyto_table_fetch(cyto_table *t, int64_t *values, int8_t *col_is_float, char 
     return CYTO_OK;
 }
 
+int cyto_table_values(cyto_table *t, const void **values_dev, int64_t *ld) {
+    if (!t || !values_dev || !ld) return CYTO_ERR_BAD_ARG;
+    *values_dev = t->values.p;
+    *ld = t->C;
+    return CYTO_OK;
+}
+
+int cyto_table_fetch_labels(cyto_table *t, int8_t *col_is_float, char *labels, double *ms_download) {
+    if (!t || !col_is_float || !labels) return CYTO_ERR_BAD_ARG;
+    int rc;
+    if ((rc = select_device(t->device_id))) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<int> dec((size_t)t->C);
+    CYTO_HIP(hipMemcpy(dec.data(), t->dec.p, (size_t)t->C * 4, hipMemcpyDeviceToHost));
+    CYTO_HIP(hipMemcpy(labels, t->labels.p, (size_t)t->label_bytes, hipMemcpyDeviceToHost));
+    for (int64_t c = 0; c < t->C; c++) col_is_float[c] = (int8_t)(dec[(size_t)c] != 0);
+    if (ms_download) *ms_download = ms_since(t0);
+    return CYTO_OK;
+}
+
 void cyto_table_free(cyto_table *t) {
     if (t && select_device(t->device_id) == CYTO_OK) delete t;
 }

@@ -59,6 +59,20 @@ def _matrix_struct(a, code):
     return m
 
 
+def _resident_matrix(frame):
+    """A resident.DeviceFrame as the matrix the host path would upload for it: the view gathered on the device into the dtype
+    _counts_matrix would choose (frame.narrowest()).  Returns (cyto_matrix with on_device = 1, the materialised frame: close it
+    after the call).  A frame that already is that matrix (no positions, that dtype) is read in place and None stands for the
+    second."""
+    dt = frame.narrowest()
+    rows, cols = frame.positions
+    own = rows is not None or cols is not None or frame.dtype != dt
+    mat = frame.materialize(dt) if own else frame
+    m = _lib.Matrix()
+    m.data, m.ld, m.is_f64, m.on_device = mat.ptr, mat.ld, _DTYPE_CODE[mat.dtype], 1
+    return m, (mat if own else None)
+
+
 def _pair(sc, st):
     """Both matrices as the boundary takes them (each in its own dtype)."""
     sc, csc = _boundary_matrix(sc)
@@ -75,19 +89,42 @@ def assign_pearson(sc, st, slots, already_normalized=True, device_id=0, return_i
     from .common import METRICS
     if distance_metric not in METRICS:
         raise ValueError(f"unknown distance_metric {distance_metric!r}")
-    sc, st, csc, cst = _pair(sc, st)
-    slots = np.ascontiguousarray(slots, dtype=np.int64)
-    G, C = sc.shape
-    S = st.shape[1]
-    if len(slots) != S:
-        raise ValueError("one slot count per spot is required")
-    mapped = np.empty(C, np.int64)
-    total = ctypes.c_double()
-    info = _lib.AssignInfo()
-    msc, mst = _matrix_struct(sc, csc), _matrix_struct(st, cst)
-    _lib.check(_lib.lib().cyto_assign_metric_ex(METRICS[distance_metric], G, ctypes.byref(msc), C, ctypes.byref(mst), S,
-                                                slots.ctypes.data, int(already_normalized), mapped.ctypes.data,
-                                                ctypes.byref(total), ctypes.byref(info), device_id))
+    from .resident import is_frame
+    held = []
+    try:
+        if is_frame(sc) or is_frame(st):          # a resident matrix is gathered on the device and read where it lies
+            if sc.shape[0] != st.shape[0]:
+                raise ValueError("The two matrices v1 and v2 must have equal dimensions; "
+                                 "ST and scRNA data must have the same genes")
+            pair = []
+            for x in (sc, st):
+                if is_frame(x):
+                    m, mat = _resident_matrix(x)
+                    held.append(mat)
+                else:
+                    x, code = _boundary_matrix(x)
+                    held.append(x)
+                    m = _matrix_struct(x, code)
+                pair.append(m)
+            msc, mst = pair
+        else:
+            sc, st, csc, cst = _pair(sc, st)
+            msc, mst = _matrix_struct(sc, csc), _matrix_struct(st, cst)
+        slots = np.ascontiguousarray(slots, dtype=np.int64)
+        G, C = sc.shape
+        S = st.shape[1]
+        if len(slots) != S:
+            raise ValueError("one slot count per spot is required")
+        mapped = np.empty(C, np.int64)
+        total = ctypes.c_double()
+        info = _lib.AssignInfo()
+        _lib.check(_lib.lib().cyto_assign_metric_ex(METRICS[distance_metric], G, ctypes.byref(msc), C, ctypes.byref(mst), S,
+                                                    slots.ctypes.data, int(already_normalized), mapped.ctypes.data,
+                                                    ctypes.byref(total), ctypes.byref(info), device_id))
+    finally:
+        for h in held:
+            if is_frame(h):
+                h.close()
     if return_info:
         return mapped, total.value, info
     return mapped
@@ -108,7 +145,8 @@ class ExpressionContext:
         self.bcast_ms = None
         self._h = ctypes.c_void_p()
         from . import common as _common
-        if _common.is_sparse(sc) or (st is not None and _common.is_sparse(st)):
+        from .resident import is_frame
+        if _common.is_sparse(sc) or (st is not None and _common.is_sparse(st)) or is_frame(sc) or is_frame(st):
             self._create_from_mixed(sc, st, already_normalized, device_id, METRICS[distance_metric], comm, root, n_spots)
             return
         sc, csc = _boundary_matrix(sc)
@@ -137,13 +175,19 @@ class ExpressionContext:
             self.bcast_ms = ms.value
 
     def _create_from_mixed(self, sc, st, already_normalized, device_id, metric, comm, root, n_spots):
-        """Inputs of which at least one is a scipy.sparse matrix: sparse ones are uploaded as non-zeros and expanded on the
-        device (cyto_csc_to_dense_f32), dense ones go up as they are (C ABI: cyto_ctx_create_ex)."""
+        """Inputs of which at least one is a scipy.sparse matrix or a resident.DeviceFrame: sparse ones are uploaded as non-zeros
+        and expanded on the device (cyto_csc_to_dense_f32), resident ones are gathered on the device into the dtype the host path
+        would upload (_resident_matrix), dense ones go up as they are (C ABI: cyto_ctx_create_ex)."""
         from . import common as _common
+        from .resident import is_frame
         keep = []
 
         def describe(x):
             m = _lib.Matrix()
+            if is_frame(x):
+                m, mat = _resident_matrix(x)
+                keep.append(mat)
+                return m, x.shape[0], x.shape[1]
             if _common.is_sparse(x):
                 buf, G, C, ld = _common.sparse_to_device(x, device_id)
                 keep.append(buf)
@@ -165,13 +209,17 @@ class ExpressionContext:
                 raise ValueError("the ST matrix (or, on non-root ranks of a communicator, n_spots) is required")
             self.S = int(n_spots)
         ms = ctypes.c_double()
-        _lib.check(_lib.lib().cyto_ctx_create_ex(metric, self.G, ctypes.byref(msc), self.C, ctypes.byref(mst) if mst is not None else None,
-                                                 self.S, int(already_normalized), comm.handle if comm is not None else None, int(root),
-                                                 comm.rank if comm is not None else 0, device_id, ctypes.byref(self._h), ctypes.byref(ms)))
+        try:
+            _lib.check(_lib.lib().cyto_ctx_create_ex(metric, self.G, ctypes.byref(msc), self.C, ctypes.byref(mst) if mst is not None else None,
+                                                     self.S, int(already_normalized), comm.handle if comm is not None else None, int(root),
+                                                     comm.rank if comm is not None else 0, device_id, ctypes.byref(self._h), ctypes.byref(ms)))
+        finally:
+            for k in keep:
+                if isinstance(k, _lib.DeviceBuffer):
+                    k.free()
+                elif is_frame(k):
+                    k.close()
         self.bcast_ms = ms.value if comm is not None else None
-        for k in keep:
-            if isinstance(k, _lib.DeviceBuffer):
-                k.free()
 
     def assign_chunks(self, chunks, max_concurrent=0, return_info=False):
         """All chunks of this rank in one call (C ABI: cyto_ctx_assign_chunks): per chunk the gathers and the cost GEMM, then
@@ -530,22 +578,58 @@ def apply_linear_assignment(scRNA_data, st_data, coordinates_data, cell_number_t
         raise ValueError("index_st_list and subsampled_cell_number_to_node_assignment_list cannot both be specified")
     if solver_method != "lapjv_hip":
         raise ValueError("apply_linear_assignment of this package drives the lapjv_hip solver")
-    sc_counts = _counts_matrix(scRNA_data.to_numpy())
-    st_counts = _counts_matrix(st_data.to_numpy()) if st_data is not None else None
+    from . import resident as _resident
+    launcher = world_size > 1 or comm is not None or device_id is not None       # the caller places this rank itself
+    plain = (index_st_list is None) and (subsampled_cell_number_to_node_assignment_list is None)
+    frames = _resident.is_frame(scRNA_data) or _resident.is_frame(st_data)
+    if frames:
+        # a resident matrix stays on the device only when ONE device of this process solves everything: no launcher arguments, and
+        # the plain form (one LAP) or a chunk fan-out that has a single device to go to
+        one = not launcher and (plain or min(len(visible_devices(devices)), len(index_sc_list)) == 1)
+        if not one or (st_data is None):
+            _resident.record_fallback("assign", "launcher" if launcher else "several devices")
+            scRNA_data = scRNA_data.to_frame() if _resident.is_frame(scRNA_data) else scRNA_data
+            st_data = st_data.to_frame() if _resident.is_frame(st_data) else st_data
+            frames = False
+    if frames:
+        sc_counts = scRNA_data if _resident.is_frame(scRNA_data) else _counts_matrix(scRNA_data.to_numpy())
+        st_counts = st_data if _resident.is_frame(st_data) else _counts_matrix(st_data.to_numpy())
+    else:
+        sc_counts = _counts_matrix(scRNA_data.to_numpy())
+        st_counts = _counts_matrix(st_data.to_numpy()) if st_data is not None else None
     cell_ids = scRNA_data.columns.values
     slots_all = np.asarray(cell_number_to_node_assignment)
-    launcher = world_size > 1 or comm is not None or device_id is not None       # the caller places this rank itself
-    if (index_st_list is None) and (subsampled_cell_number_to_node_assignment_list is None):
+    if plain:
         print('Solving linear assignment problem ...')
         t0 = time.perf_counter()
         one_dev = (0 if device_id is None else device_id) if launcher else visible_devices(devices)[0]   # one LAP: one GPU
-        mapped = assign_pearson(sc_counts[:, index_sc_list[0]], st_counts, slots_all, already_normalized=False,
-                                device_id=one_dev, distance_metric=distance_metric)
+        if _resident.is_frame(sc_counts):
+            # the host path narrows ALL the sampled columns and then takes the listed ones: the same dtype, the same values
+            dt = sc_counts.narrowest()
+            sc_chunk = sc_counts.take(cols=index_sc_list[0]).materialize(dt)
+        else:
+            sc_chunk = sc_counts[:, index_sc_list[0]]
+        try:
+            mapped = assign_pearson(sc_chunk, st_counts, slots_all, already_normalized=False,
+                                    device_id=one_dev, distance_metric=distance_metric)
+        finally:
+            if _resident.is_frame(sc_chunk):
+                sc_chunk.close()
         print(f"Time to solve linear assignment problem: {round(time.perf_counter() - t0, 2)} seconds")
         return coordinates_data.iloc[mapped.tolist()], cell_ids[index_sc_list[0]]
     n_chunks = len(index_st_list) if index_st_list is not None else len(subsampled_cell_number_to_node_assignment_list)
     print(f"Number of required processors: {n_chunks}")
-    if launcher:
+    if frames:
+        # what assign_chunks does with one device and every chunk its own: one context, all chunks in one batched call
+        with ExpressionContext(sc_counts, st_counts, False, visible_devices(devices)[0], distance_metric) as ctx:
+            chunks = []
+            for idx in range(len(index_sc_list)):
+                if index_st_list is not None:
+                    chunks.append((index_sc_list[idx], slots_all[np.asarray(index_st_list[idx])], index_st_list[idx]))
+                else:
+                    chunks.append((index_sc_list[idx], subsampled_cell_number_to_node_assignment_list[idx], None))
+            res = dict(enumerate(ctx.assign_chunks(chunks, int(number_of_processors))))
+    elif launcher:
         res = assign_chunks(sc_counts, st_counts, slots_all, index_sc_list, index_st_list,
                             subsampled_cell_number_to_node_assignment_list, rank=rank, world_size=world_size,
                             device_id=0 if device_id is None else device_id, max_concurrent=int(number_of_processors),
@@ -623,8 +707,12 @@ def _sample_single_cells(scRNA_data, cell_type_data, cell_type_numbers_int, samp
     genes x short float64 block of synthetic cells from numpy's global generator."""
     import random
     import pandas as pd
+    from . import resident as _resident
     if sampling_method not in ("duplicates", "place_holders"):
         raise ValueError("Invalid sampling_method provided")
+    if _resident.is_frame(scRNA_data) and sampling_method == "place_holders":
+        _resident.record_fallback("sample", "place_holders")     # (the synthetic cells are built from host blocks)
+        scRNA_data = scRNA_data.to_frame()
     np.random.seed(seed)
     random.seed(seed)
     labels = cell_type_data.values[:, 0]
@@ -653,6 +741,8 @@ def _sample_single_cells(scRNA_data, cell_type_data, cell_type_numbers_int, samp
             blocks.append(own); blocks.append(fake)
     if sampling_method == "place_holders":
         return pd.DataFrame(np.concatenate(blocks, axis=1), index=scRNA_data.index, columns=np.concatenate(names, axis=0))
+    if _resident.is_frame(scRNA_data):
+        return scRNA_data.take(cols=np.concatenate(picked, axis=0).astype(int))
     return scRNA_data.iloc[:, np.concatenate(picked, axis=0).astype(int)]
 
 
@@ -661,15 +751,20 @@ def _sample_single_cells(scRNA_data, cell_type_data, cell_type_numbers_int, samp
 
 def read_data(scRNA_path, cell_type_path, cell_type_fraction_estimation_path, n_cells_per_spot_path,
               st_cell_type_path, output_path, output_prefix, spaceranger_path=None, st_path=None, coordinates_path=None,
-              device_id=0):
+              device_id=0, resident=False):
     """cytospace.py:20-113.  Reads the inputs and prefixes their ids (spots 'SPOT_', cells 'CELL_', genes 'GENE_', cell
     types 'TYPE_'), drops genes listed more than once, orders ST and scRNA columns like the coordinates and cell-type
     tables, and validates.  The two expression inputs (scRNA_path, st_path) are parsed on GPU device_id: delimited text by
     common.read_file_device, a MatrixMarket `.mtx` with its gene and cell lists by common.read_mtx_device (the same DataFrames
     as read_file, a MatrixMarket input dense as the reference reads it; a file outside their grammars is read by read_file);
     the small tables are read by read_file.  Unlike the
-    reference this never reads a Space Ranger archive or estimates fractions with R: both raise ValueError (see check_supported)."""
+    reference this never reads a Space Ranger archive or estimates fractions with R: both raise ValueError (see check_supported).
+
+    resident=True: the two expression tables come back as resident.DeviceFrame where one can stand for them (a text table of one
+    column kind keeps its parsed values in HBM; a MatrixMarket input is uploaded once) -- the label work below is the same host
+    code, applied to the frames with `take`; a table a frame cannot stand for stays a DataFrame (resident.last_run says which)."""
     from .common import read_file, read_file_device, read_mtx_device
+    from . import resident as _resident
     check_supported(spaceranger_path=spaceranger_path, st_cell_type_path=st_cell_type_path,
                     cell_type_fraction_estimation_path=cell_type_fraction_estimation_path)
     if (st_path is None) and (coordinates_path is None):
@@ -678,22 +773,48 @@ def read_data(scRNA_path, cell_type_path, cell_type_fraction_estimation_path, n_
     def read(path):
         return read_file(path, keep_sparse=False)
 
-    def read_expression(path):
+    def read_expression(path, name):
+        if not resident:
+            if isinstance(path, str) and path.endswith(".mtx"):
+                return read_mtx_device(path, device_id)
+            return read_file_device(path, device_id)
         if isinstance(path, str) and path.endswith(".mtx"):
-            return read_mtx_device(path, device_id)
-        return read_file_device(path, device_id)
+            x, why = read_mtx_device(path, device_id), None
+            try:
+                x = _resident.DeviceFrame.from_frame(x, device_id)
+            except TypeError as e:
+                why = str(e)
+        else:
+            x, info = read_file_device(path, device_id, return_info=True, resident=True)
+            why = None if info["resident"] else info.get("resident_reason", info.get("reason", {}).get("kind", "host"))
+        if _resident.is_frame(x):
+            _resident.last_run[name] = x.stats
+        else:
+            _resident.last_run[name] = {"source": "host", "fetches": 0, "materialized": 0}
+            _resident.record_fallback("read " + name, why)
+        return x
 
-    st_data = read_expression(st_path)
+    def unique_genes(x):
+        keep = ~x.index.duplicated(keep=False)
+        if not _resident.is_frame(x):
+            return x[keep]
+        return x if keep.all() else x.take(rows=np.flatnonzero(keep))
+
+    def ordered(x, labels):
+        """x[labels] (columns by label; KeyError for a missing one)."""
+        return x.take_labels(columns=labels) if _resident.is_frame(x) else x[labels]
+
+    st_data = read_expression(st_path, "ST")
     coordinates_data = read(coordinates_path)
-    st_data = st_data[~st_data.index.duplicated(keep=False)]
+    st_data = unique_genes(st_data)
     st_data.columns = ["SPOT_" + str(c) for c in st_data.columns]
     st_data.index = ["GENE_" + str(g) for g in st_data.index]
     coordinates_data.index = ["SPOT_" + str(s) for s in coordinates_data.index]
 
-    scRNA_data = read_expression(scRNA_path)
+    scRNA_data = read_expression(scRNA_path, "scRNA")
     scRNA_data.columns = ["CELL_" + str(c) for c in scRNA_data.columns]
     scRNA_data.index = ["GENE_" + str(g) for g in scRNA_data.index]
-    scRNA_data = scRNA_data[~scRNA_data.index.duplicated(keep=False)]
+    scRNA_data = unique_genes(scRNA_data)
 
     cell_type_data = read(cell_type_path)
     cell_type_data.index = ["CELL_" + str(c) for c in cell_type_data.index]
@@ -714,8 +835,8 @@ def read_data(scRNA_path, cell_type_path, cell_type_fraction_estimation_path, n_
         n_cells_per_spot_data.index = ["SPOT_" + str(s) for s in n_cells_per_spot_data.index]
 
     try:
-        st_data = st_data[coordinates_data.index]
-        scRNA_data = scRNA_data[cell_type_data.index]
+        st_data = ordered(st_data, coordinates_data.index)
+        scRNA_data = ordered(scRNA_data, cell_type_data.index)
         if st_cell_type_data is not None:
             st_cell_type_data = st_cell_type_data.loc[coordinates_data.index, :]
         if n_cells_per_spot_data is not None:
@@ -765,18 +886,27 @@ def main_cytospace(scRNA_path, cell_type_path,
                    single_cell=False, number_of_selected_spots=10000,
                    sampling_sub_spots=False, number_of_selected_sub_spots=10000,
                    number_of_processors=1, seed=1,
-                   plot_off=False, geometry="honeycomb", max_num_cells_plot=50000, num_column=3, devices=None):
+                   plot_off=False, geometry="honeycomb", max_num_cells_plot=50000, num_column=3, devices=None, resident=None):
     """cytospace.py:472-717 with the same arguments (plus `devices`, see apply_linear_assignment) and the same random-number
     use: both generators seeded, then cells per spot, cell type numbers, the gene intersection, the downsampling (on the GPU,
     the same draws as the host's), sample_single_cells (its place-holder cells drawn on the GPU, again the host's draws) and the
     partitions; then every chunk on the GPU solver and the
-    reference's output files and log.  Plots are not produced (the plotting arguments are accepted and logged)."""
+    reference's output files and log.  Plots are not produced (the plotting arguments are accepted and logged).
+
+    resident (None: the environment variable CYTOSPACE_HIP_RESIDENT, "1" means on; the default is off): the two expression tables
+    stay in HBM from the reader to the solver and the writer (resident.DeviceFrame) -- the same files, byte for
+    byte; resident.last_run reports what stayed on the device and what went through the host."""
     import random
     import pandas as pd
     from .common import check_paths, downsample_device
     from .post_processing import save_results, save_unassigned_locations
 
+    from . import resident as _resident
     check_supported(solver_method, spaceranger_path, st_cell_type_path, cell_type_fraction_estimation_path)
+    if resident is None:
+        resident = os.environ.get("CYTOSPACE_HIP_RESIDENT", "").strip() == "1"
+    if resident:
+        _resident.last_run = {"scRNA": None, "ST": None, "fallbacks": []}
     start_time = time.perf_counter()
     output_path = check_paths(output_folder, output_prefix)
     fout_log = os.path.join(output_path, f"{output_prefix}log.txt")
@@ -804,7 +934,8 @@ def main_cytospace(scRNA_path, cell_type_path,
     t0 = time.perf_counter()
     scRNA_data, cell_type_data, st_data, coordinates_data, cell_type_fractions_data, n_cells_per_spot_data, st_cell_type_data = \
         read_data(scRNA_path, cell_type_path, cell_type_fraction_estimation_path, n_cells_per_spot_path, st_cell_type_path,
-                  output_path, output_prefix, spaceranger_path, st_path, coordinates_path, device_id=device)
+                  output_path, output_prefix, spaceranger_path, st_path, coordinates_path, device_id=device,
+                  **(dict(resident=True) if resident else {}))
     all_spot_ids = st_data.columns
     print(f"Time to read and validate data: {round(time.perf_counter() - t0, 2)} seconds")
     log(f"Time to read and validate data: {round(time.perf_counter() - t0, 2)} seconds\n")
@@ -817,7 +948,8 @@ def main_cytospace(scRNA_path, cell_type_path,
         cell_number_to_node_assignment = np.ones(st_data.shape[1]).astype(int)
     elif n_cells_per_spot_data is None:
         print("Estimating number of cells in each spot ...")
-        cell_number_to_node_assignment = estimate_cell_number_RNA_reads(st_data, mean_cell_numbers, device)
+        cell_number_to_node_assignment = estimate_cell_number_RNA_reads(
+            st_data.to_frame() if _resident.is_frame(st_data) else st_data, mean_cell_numbers, device)
         print(f"Time to estimate number of cells per spot: {round(time.perf_counter() - t0_core, 2)} seconds")
     else:
         cell_number_to_node_assignment = n_cells_per_spot_data.values[:, 0].astype(int)
@@ -836,8 +968,9 @@ def main_cytospace(scRNA_path, cell_type_path,
     print("Down/up sample of scRNA-seq data according to estimated cell type fractions")
     t0 = time.perf_counter()
     intersect_genes = st_data.index.intersection(scRNA_data.index)
-    scRNA_data_sampled = scRNA_data.loc[intersect_genes, :]
-    st_data = st_data.loc[intersect_genes, :]
+    scRNA_data_sampled = scRNA_data.take_labels(index=intersect_genes) if _resident.is_frame(scRNA_data) \
+        else scRNA_data.loc[intersect_genes, :]
+    st_data = st_data.take_labels(index=intersect_genes) if _resident.is_frame(st_data) else st_data.loc[intersect_genes, :]
     if not downsample_off:
         scRNA_data_sampled = downsample_device(scRNA_data_sampled, scRNA_max_transcripts_per_cell, device_id=device)
     log("Number of genes used for mapping: " + str(len(intersect_genes)) + "\n")
@@ -895,6 +1028,9 @@ def main_cytospace(scRNA_path, cell_type_path,
     save_results(output_path, output_prefix, cell_ids_selected,
                  scRNA_data_sampled if sampling_method == "place_holders" else scRNA_data,
                  assigned_locations, cell_type_data, sampling_method, single_cell, device_id=device)
+    for x in (scRNA_data_sampled, scRNA_data, st_data):
+        if _resident.is_frame(x):
+            x.close()
     if not plot_off:
         print("Plotting is not part of this package: no plots are produced (the results are written as files).")
     print(f"Total execution time: {round(time.perf_counter() - start_time, 2)} seconds")

@@ -87,6 +87,10 @@ def write_mtx_device(path, matrix_or_frame, columns, device_id=0, block_bytes=0,
     value, by the shortest digits that read back as the same value of the matrix's dtype, as scipy does ("1E-1", "2.5",
     "3.333333333333333E-1", "5E-324"); of the real values only NaN and +-inf ("non-finite value") still go to scipy.
 
+    matrix_or_frame may be a resident.DeviceFrame: the values are read where they lie in HBM (C ABI: cyto_mtx_write_dev; a frame
+    that is a view of some of its buffer's rows is gathered on the device first), the same bytes; what the device refuses -- a
+    square result, a non-finite value -- is written by scipy from the fetched frame (noted in resident.last_run["fallbacks"]).
+
     return_info: also return a dict -- "path" ("device" or "scipy"), for a fallback "reason", and for the device "nnz", "bytes",
     "field", "blocks" and the phase times in seconds: narrow_s (the host's choice of the upload dtype), library_s (the whole
     cyto_mtx_write call: device and pinned allocations and their release besides the next four), upload_s, kernels_s, download_s
@@ -98,8 +102,10 @@ def write_mtx_device(path, matrix_or_frame, columns, device_id=0, block_bytes=0,
     import scipy.sparse
     t0 = time.perf_counter()
     info = {"path": "device"}
+    from . import resident as _resident
+    dframe = matrix_or_frame if _resident.is_frame(matrix_or_frame) else None
     frame = matrix_or_frame if isinstance(matrix_or_frame, pd.DataFrame) else None
-    if frame is None:
+    if frame is None and dframe is None:
         matrix_or_frame = np.asarray(matrix_or_frame)
         if matrix_or_frame.ndim != 2:
             raise ValueError("write_mtx_device needs a 2-D matrix")
@@ -111,9 +117,13 @@ def write_mtx_device(path, matrix_or_frame, columns, device_id=0, block_bytes=0,
     C = len(columns)
 
     def selected():
+        if dframe is not None:
+            return dframe.take(cols=columns).to_frame()
         return frame.iloc[:, columns] if frame is not None else matrix_or_frame[:, columns]
 
     def refuse(reason):
+        if dframe is not None:
+            _resident.record_fallback("write_mtx", reason)
         info.update(path="scipy", reason=reason)
         scipy.io.mmwrite(path, scipy.sparse.coo_matrix(selected()))
         info["total_s"] = time.perf_counter() - t0
@@ -125,6 +135,32 @@ def write_mtx_device(path, matrix_or_frame, columns, device_id=0, block_bytes=0,
         return refuse("empty")
     if G == C:
         return refuse("square")
+    if dframe is not None:
+        if not dframe.columns.is_unique:
+            return refuse("duplicate labels")
+        # the buffer itself when the view keeps every row (the column positions go through the view's own); else one gather
+        rows, cols = dframe.positions
+        mat = dframe if rows is None else dframe.take(cols=columns).materialize()
+        try:
+            if rows is not None:
+                src, N0 = np.arange(C, dtype=np.int64), C
+            else:
+                src, N0 = np.ascontiguousarray(columns if cols is None else cols[columns]), dframe.buffer_shape[1]
+            mi = _lib.MtxInfo()
+            t = time.perf_counter()
+            st = _lib.lib().cyto_mtx_write_dev(path.encode(), G, N0, mat.ptr, mat.ld, mat.code, src.ctypes.data, C, int(block_bytes),
+                                               device_id, _lib.CYTO_TEXT_FRACTIONS if fractions else 0, ctypes.byref(mi))
+            info["library_s"] = time.perf_counter() - t
+        finally:
+            if mat is not dframe:
+                mat.close()
+        if st == _lib.CYTO_ERR_UNSUPPORTED:                                  # nothing is left at `path`
+            return refuse(_MTX_REFUSALS.get(mi.reason, str(mi.reason)))
+        _lib.check(st)
+        info.update(nnz=mi.nnz, bytes=mi.bytes, field="real" if mi.field else "integer", blocks=mi.blocks, upload_s=mi.ms_upload / 1e3,
+                    kernels_s=mi.ms_kernels / 1e3, download_s=mi.ms_download / 1e3, write_s=mi.ms_write / 1e3)
+        info["total_s"] = time.perf_counter() - t0
+        return info if return_info else None
     if frame is not None:
         if not frame.columns.is_unique:
             return refuse("duplicate labels")
@@ -317,6 +353,9 @@ def save_results(output_path, output_prefix, cell_ids_selected, all_cells_save, 
       <prefix>cell_type_assignments_by_spot.csv, <prefix>fractional_abundances_by_spot.csv   (not in single-cell mode)"""
     import scipy.io
     import scipy.sparse
+    from . import resident as _resident
+    if _resident.is_frame(all_cells_save) and (device_id is None or sampling_method != "duplicates"):
+        all_cells_save = all_cells_save.to_frame()
     df = assigned_locations_table(cell_ids_selected, assigned_locations, cell_type_data, sampling_method)
     df.to_csv(os.path.join(output_path, f"{output_prefix}assigned_locations.csv"), index=False)
 
@@ -332,6 +371,9 @@ def save_results(output_path, output_prefix, cell_ids_selected, all_cells_save, 
             if (positions < 0).any():                     # (a missing label: the host path raises its KeyError)
                 positions = None
         if positions is None:
+            if _resident.is_frame(all_cells_save):
+                _resident.record_fallback("save_results", "labels")
+                all_cells_save = all_cells_save.to_frame()
             expr = all_cells_save.loc[:, labels]
             expr.index = _strip("GENE_", expr.index)
             expr.columns = df.UniqueCID

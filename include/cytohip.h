@@ -462,8 +462,10 @@ int cyto_assign_metric_typed(int metric, int G, int C, int S, const void *sc, co
                              cyto_assign_info *info, int device_id);
 int cyto_ctx_create_typed(int metric, int G, int C, int S, const void *sc, const void *st, int x_is_f64,
                           int already_normalized, int device_id, cyto_expr_ctx **out);
-/* ... and with an element type PER MATRIX (host matrices, ld == columns): scRNA counts as uint8 beside ST counts as uint16, say --
- * what cytospace_amd.cytospace.assign_pearson passes for integer count matrices (config c3: the upload bounds the call). */
+/* ... and with an element type PER MATRIX: scRNA counts as uint8 beside ST counts as uint16, say -- what
+ * cytospace_amd.cytospace.assign_pearson passes for integer count matrices (config c3: the upload bounds the call).  A host matrix has
+ * ld == columns; a matrix with on_device = 1 (any ld >= columns; complete before the call, which runs on a private stream) is
+ * transformed where it lies, with the same results bit for bit. */
 int cyto_assign_metric_ex(int metric, int G, const cyto_matrix *sc, int C, const cyto_matrix *st, int S, const int64_t *slots,
                           int already_normalized, int64_t *mapped_spot, double *total_cost, cyto_assign_info *info, int device_id);
 
@@ -478,6 +480,11 @@ int cyto_assign_metric_ex(int metric, int G, const cyto_matrix *sc, int C, const
  * downsampled cell with T > 2^32 when target > 0 (numpy draws 64-bit words there), a bad dtype or size. */
 int cyto_downsample(int G, int C, const void *x, int64_t ldx, int x_dtype, void *out, int64_t ldo, int out_dtype, int target,
                     uint32_t *key, int32_t *pos, int64_t *words_out, int device_id);
+/* The same with x and out ALREADY ON THE DEVICE (two distinct buffers, any leading dimensions >= C): the same kernels, draws, key / pos /
+ * words semantics and CYTO_ERR_BAD_ARG cases (and x_dev == out_dev); nothing but the per-cell totals and the generator's state crosses
+ * PCIe.  Returns with out_dev complete. */
+int cyto_downsample_dev(int G, int C, const void *x_dev, int64_t ldx, int x_dtype, void *out_dev, int64_t ldo, int out_dtype, int target,
+                        uint32_t *key, int32_t *pos, int64_t *words_out, int device_id);
 /* ---- place-holder cells (cytospace/cytospace.py:212-301, sampling_method "place_holders"): short_count synthetic cells of a cell
  * type with n cells, gene g of each drawn independently from the type's n values of that gene -- the reference's
  * fake[:, k] = [np.random.choice(own[g, :]) for g in range(G)], k = 0 .. short_count-1, with exactly the words numpy's legacy global
@@ -523,6 +530,11 @@ int cyto_table_read(const char *path, char sep, int64_t data_offset, int64_t nco
 /* values: G x C int64 words, row-major (a float64 column's words are its values' bits); col_is_float: C flags; labels: the row
  * labels, each followed by sep and '\n' (shape[2] bytes); *ms_download (may be NULL). */
 int cyto_table_fetch(cyto_table *t, int64_t *values, int8_t *col_is_float, char *labels, double *ms_download);
+/* The parsed values where they lie (cytospace_amd.resident.DeviceFrame): *values_dev is a BORROWED device pointer to the G x C int64
+ * words, row-major with leading dimension *ld, valid until cyto_table_free; no device is touched.  cyto_table_fetch_labels is
+ * cyto_table_fetch without the values. */
+int cyto_table_values(cyto_table *t, const void **values_dev, int64_t *ld);
+int cyto_table_fetch_labels(cyto_table *t, int8_t *col_is_float, char *labels, double *ms_download);
 void cyto_table_free(cyto_table *t);
 /* The converter alone, on the host (a test hook): token i is text[offsets[i], offsets[i+1]); kinds[i] 0 integer token (ints[i],
  * and values[i] as a decimal), 1 decimal token (values[i]), 2 outside the token grammar, 3 out of range. */
@@ -581,6 +593,10 @@ int cyto_mtx_write(const char *path, int64_t G, int64_t N, const void *x, int64_
 /* The same with flags (CYTO_TEXT_FRACTIONS: no real value but a NaN or an infinity is refused); cyto_mtx_write is flags = 0. */
 int cyto_mtx_write_ex(const char *path, int64_t G, int64_t N, const void *x, int64_t ldx, int x_dtype, const int64_t *cols, int64_t C,
                       int64_t block_bytes, int device_id, int flags, cyto_mtx_info *info);
+/* The same with x ALREADY ON THE DEVICE (G x ldx elements, read where they lie): the same bytes; info->ms_upload counts the column
+ * list only.  flags as cyto_mtx_write_ex's (the device form adds no bit). */
+int cyto_mtx_write_dev(const char *path, int64_t G, int64_t N, const void *x_dev, int64_t ldx, int x_dtype, const int64_t *cols, int64_t C,
+                       int64_t block_bytes, int device_id, int flags, cyto_mtx_info *info);
 /* The formatter alone, on the host (a test hook): entry i is (rows[i], cols[i], values[i]), 0-based, values of CYTO_DTYPE_* dtype; its
  * line is out[offsets[i], offsets[i + 1]) -- empty for a zero, which the writer skips.  out holds 64 * n bytes, offsets n + 1 words.
  * CYTO_ERR_UNSUPPORTED at the first real value outside the device grammar. */
@@ -677,6 +693,36 @@ int cyto_mtx_read(const char *path, int64_t data_offset, int64_t G, int64_t C, i
  * values[i] the int64 value or the float64 bits (kind 0). */
 int cyto_mtx_parse_entries(const char *text, int64_t n, const int64_t *offsets, int field, int64_t G, int64_t C, int8_t *kinds,
                            int64_t *where, int64_t *rows, int64_t *cols, int64_t *values);
+
+/* ---- a table that stays in HBM between the stages (cytospace_amd.resident.DeviceFrame).  A VIEW is rows and columns
+ * of a row-major device matrix: src_dev (G x C, leading dimension ld_src >= C, of src_dtype), rows (host, Gs positions in [0, G); NULL:
+ * all G rows in order, Gs == G) and cols (host, Cs positions in [0, C); NULL: all C columns in order, Cs == C); repeats allowed in both.
+ *
+ * cyto_select: dst[i][j] = (dst type) src[rows[i]][cols[j]], device to device, into dst_dev (Gs x ld_dst, ld_dst >= Cs; the columns
+ * Cs ... ld_dst-1 are not written; dst_dev must not overlap src_dev).  src_dtype: CYTO_DTYPE_I64, _F64 (cyto_table's two column
+ * kinds), _U16, _F32; dst_dtype: _U8, _U16, _I64, _F32, _F64.  *inexact: the elements whose value does not survive the conversion
+ * (numpy's round trip v.astype(dst).astype(src) == v: a fraction or a value out of range for an integer type, an integer beyond
+ * float32's / float64's 24 / 53 bits, a float64 that is no float32 -- and any NaN, which equals nothing).  Where *inexact > 0 the
+ * inexact elements of an integer destination are unspecified and the caller discards the result; a float32 / float64 destination
+ * always holds the rounded values (a same-type select copies the bits, NaN included).  All offsets are 64-bit.
+ * CYTO_ERR_BAD_ARG, before a device is touched: a position outside its range, a dtype outside the lists, ld < columns, a negative extent,
+ * a NULL list with Gs != G / Cs != C, a null pointer with a non-zero extent.  Gs == 0 or Cs == 0: CYTO_OK, nothing launched.
+ * stream: as above (NULL: the default stream); the call returns with dst_dev complete.
+ *
+ * cyto_value_range: one pass over the same view, what cytospace_amd.cytospace._counts_matrix looks at to choose its dtype: *lo / *hi
+ * the least and the largest value (NaNs skipped; +inf / -inf for an empty view or one of NaNs only), for the integer sources also
+ * exactly in *lo_i64 / *hi_i64 (may be NULL; INT64_MAX / INT64_MIN for an empty view); *non_integral finite values with a fraction,
+ * *non_finite NaNs and infinities, *not_f32_exact values other than NaN that float32 does not hold.  Order-free: minima, maxima, counts.
+ *
+ * cyto_select_check: the predicate alone, on the host (a test hook; no device): ok[i] = values[i] (src_dtype) survives the conversion
+ * to dst_dtype.  It is the function the kernel calls (csrc/select_exact.h). */
+int cyto_select(int64_t G, int64_t C, const void *src_dev, int64_t ld_src, int src_dtype, const int64_t *rows, int64_t Gs,
+                const int64_t *cols, int64_t Cs, void *dst_dev, int64_t ld_dst, int dst_dtype, int64_t *inexact, int device_id,
+                void *stream);
+int cyto_value_range(int64_t G, int64_t C, const void *src_dev, int64_t ld_src, int src_dtype, const int64_t *rows, int64_t Gs,
+                     const int64_t *cols, int64_t Cs, double *lo, double *hi, int64_t *lo_i64, int64_t *hi_i64, int64_t *non_integral,
+                     int64_t *non_finite, int64_t *not_f32_exact, int device_id, void *stream);
+int cyto_select_check(const void *values, int src_dtype, int64_t n, int dst_dtype, int8_t *ok);
 
 #ifdef __cplusplus
 }
