@@ -9,9 +9,11 @@ The in-flight input.  On one non-blocking stream s of the test's own:
   3. behind it, the device-to-device copy that overwrites the decoy with the payload (uploaded beforehand, synchronously, into another
      buffer);
   4. the entry point is called with stream = s at once, without synchronising.
-The result must be the payload's: the CPU oracle's bits for the LAPs, the bits of the same call on the NULL stream with settled inputs
-for the rest.  Device outputs are read right after the call with plain cyto_memcpy_d2h (a synchronous copy on the NULL stream, which a
-non-blocking stream does not wait for): they must be complete.
+The result must be the payload's: the CPU oracle's bits for the LAPs (cyto_lap_f32, cyto_lap_f32_opts, cyto_lap_f64,
+cyto_lap_f32_rowmap), numpy's own for the views of a resident table (cyto_select: src[ix_(rows, cols)].astype; cyto_value_range: the
+payload's minimum, maximum and counts), the bits of the same call on the NULL stream with settled inputs for the rest (cyto_transform,
+cyto_cost_metric; cyto_csc_to_dense_f32 has host inputs).  Device outputs are read right after the call with plain cyto_memcpy_d2h (a
+synchronous copy on the NULL stream, which a non-blocking stream does not wait for): they must be complete.
 
 The premise is a condition, not a skip: right before the call hipStreamQuery(s) must say not-ready, and the event-measured delay must
 be at least ten times the host-measured gap between the last enqueue's return and the library call -- else the test FAILS.
@@ -343,3 +345,102 @@ def test_csc_to_dense_on_the_callers_stream(flight):
     finally:
         hip.stream_synchronize(flight.s)
         buf.free()
+
+
+# ---- views of a resident table (cyto_select, cyto_value_range) ---------------------------------------------------------------
+
+VIEW_G, VIEW_C = 700, 333
+
+
+def _view_tables():
+    """(payload, decoy): float64 tables of one shape; the decoy is finite, holds other values everywhere and has another range."""
+    rng = np.random.default_rng(92)
+    payload = rng.poisson(3.0, (VIEW_G, VIEW_C)).astype(np.float64)
+    payload[rng.integers(0, VIEW_G, 50), rng.integers(0, VIEW_C, 50)] = 0.5          # not integral
+    payload[rng.integers(0, VIEW_G, 30), rng.integers(0, VIEW_C, 30)] = 0.1          # ... and no float32 value
+    payload[VIEW_G - 1, VIEW_C - 1], payload[0, 0] = 60000.0, -2.0
+    decoy = rng.integers(1000, 2000, (VIEW_G, VIEW_C)).astype(np.float64)
+    assert (payload != decoy).all()
+    return payload, decoy
+
+
+def _view_lists():
+    rng = np.random.default_rng(93)
+    rows = np.ascontiguousarray(np.r_[rng.integers(0, VIEW_G, 400), VIEW_G - 1, 0].astype(np.int64))
+    cols = np.ascontiguousarray(np.r_[VIEW_C - 1, rng.integers(0, VIEW_C, 200), 0].astype(np.int64))
+    return [(None, None), (rows, cols)]          # (without lists first: nothing but the table is in flight then)
+
+
+@pytest.mark.parametrize("dst", ["float32", "uint16"])
+def test_select_reads_its_table_behind_the_callers_queue(flight, dst):
+    from test_resident_select_gpu import DST, SRC, expect
+    payload, decoy = _view_tables()
+    x = InFlight(payload, decoy)
+    try:
+        for rows, cols in _view_lists():
+            Gs, Cs = (VIEW_G if rows is None else len(rows)), (VIEW_C if cols is None else len(cols))
+            ix = np.ix_(np.arange(VIEW_G) if rows is None else rows, np.arange(VIEW_C) if cols is None else cols)
+            want, ok, defined = expect(payload[ix], dst)
+            want_decoy, _, _ = expect(decoy[ix], dst)
+            assert defined.mean() > 0.9 and (want[defined] != want_decoy[defined]).all()
+            ld_dst = Cs + 3
+            out = _lib.DeviceBuffer.from_numpy(np.full(Gs * ld_dst * np.dtype(DST[dst][0]).itemsize, 0xA5, np.uint8))
+            bad = ctypes.c_int64(-7)
+
+            def call(s):
+                st = _lib.lib().cyto_select(VIEW_G, VIEW_C, x.target.ptr, VIEW_C, SRC["float64"][1], None if rows is None else rows.ctypes.data, Gs,
+                                            None if cols is None else cols.ctypes.data, Cs, out.ptr, ld_dst, DST[dst][1], ctypes.byref(bad), 0, s)
+                return st, out.to_numpy((Gs, ld_dst), DST[dst][0])             # (plain cyto_memcpy_d2h, at once)
+
+            name = f"cyto_select float64 -> {dst}" + ("" if rows is None else " with lists")
+            try:
+                (st, got), premise = flight.run(name, [x.copy], call)
+                premise()
+                assert st == 0
+                block = got[:, :Cs]
+                n_decoy = int((block[defined] == want_decoy[defined]).sum())
+                assert np.array_equal(block[defined].view(np.uint8), want[defined].view(np.uint8)), \
+                    (name, f"{(block[defined] != want[defined]).sum()} elements are not the payload's; {n_decoy} are the decoy's")
+                assert bad.value == int(np.count_nonzero(~ok)), (name, bad.value)
+                assert (np.ascontiguousarray(got[:, Cs:]).view(np.uint8) == 0xA5).all(), (name, "padding written")
+            finally:
+                hip.stream_synchronize(flight.s)
+                out.free()
+            _lib.check(_lib.lib().cyto_memcpy_h2d(x.target.ptr, decoy.ctypes.data, decoy.nbytes, 0))      # (the next round starts from the decoy)
+    finally:
+        hip.stream_synchronize(flight.s)
+        x.free()
+
+
+def test_value_range_reads_its_table_behind_the_callers_queue(flight):
+    from test_resident_select_gpu import SRC, expect_range
+    payload, decoy = _view_tables()
+    x = InFlight(payload, decoy)
+    try:
+        for rows, cols in _view_lists():
+            Gs, Cs = (VIEW_G if rows is None else len(rows)), (VIEW_C if cols is None else len(cols))
+            ix = np.ix_(np.arange(VIEW_G) if rows is None else rows, np.arange(VIEW_C) if cols is None else cols)
+            want, want_decoy = expect_range(payload[ix]), expect_range(decoy[ix])
+            assert all(want[k] != want_decoy[k] for k in ("lo", "hi", "non_integral", "not_f32_exact"))
+
+            def call(s):
+                lo, hi = ctypes.c_double(), ctypes.c_double()
+                ilo, ihi, nint, nfin, n32 = (ctypes.c_int64(-7) for _ in range(5))
+                st = _lib.lib().cyto_value_range(VIEW_G, VIEW_C, x.target.ptr, VIEW_C, SRC["float64"][1], None if rows is None else rows.ctypes.data,
+                                                 Gs, None if cols is None else cols.ctypes.data, Cs, ctypes.byref(lo), ctypes.byref(hi),
+                                                 ctypes.byref(ilo), ctypes.byref(ihi), ctypes.byref(nint), ctypes.byref(nfin), ctypes.byref(n32), 0, s)
+                return st, dict(lo=lo.value, hi=hi.value, ilo=ilo.value, ihi=ihi.value, non_integral=nint.value, non_finite=nfin.value,
+                                not_f32_exact=n32.value)
+
+            name = "cyto_value_range float64" + ("" if rows is None else " with lists")
+            try:
+                (st, got), premise = flight.run(name, [x.copy], call)
+                premise()
+                assert st == 0
+                assert got == want, (name, got, "the decoy's" if got == want_decoy else "neither")
+            finally:
+                hip.stream_synchronize(flight.s)
+            _lib.check(_lib.lib().cyto_memcpy_h2d(x.target.ptr, decoy.ctypes.data, decoy.nbytes, 0))      # (the next round starts from the decoy)
+    finally:
+        hip.stream_synchronize(flight.s)
+        x.free()

@@ -1,7 +1,9 @@
 """cyto_select and cyto_value_range (csrc/resident.hip) on the GPU against numpy: dst = src[np.ix_(rows, cols)].astype(dst type),
 for every source and destination type, with and without row and column lists, in the 16-byte and the one-element forms of the
-kernel; the count of values that do not survive the conversion; untouched padding; the refusals; poisoned work buffers; and one
-table whose element offsets pass 2^31.  Integer data and byte comparisons: nothing has a tolerance."""
+kernel; the count of values that do not survive the conversion; untouched padding; the refusals; poisoned work buffers; one
+table whose element offsets pass 2^31; tables with more rows than the launches have row blocks (4 096 / 256: the stride loops every
+real table takes); every workgroup size and a partial last lane in both forms; and each alignment condition of the 16-byte form
+broken alone.  Integer data and byte comparisons: nothing has a tolerance."""
 import ctypes
 import warnings
 
@@ -259,3 +261,212 @@ def test_offsets_beyond_two_to_the_31(hip_lib):
         assert (r["ilo"], r["ihi"]) == (0, int(want.max()))
     finally:
         buf.free()
+
+
+# ---- the row stride loops, the lane and workgroup edges, the wide form's preconditions --------------------------------------------
+
+PLANTED = {"uint16": [255, 256, 65535, 0],
+           "int64": [-1, 255, 256, 65535, 65536, 2**24, 2**24 + 1, 2**53 + 1, -(2**63), 2**63 - 1],
+           "float32": [-1, 255, 256, 65535, 65536, 2**24, 2**24 + 2, 0.5, -0.0, np.inf, -np.inf, np.nan],
+           "float64": [-1, 255, 256, 65535, 65536, 2**24, 2**24 + 1, 0.5, -0.0, np.inf, -np.inf, np.nan, 2.0**53 + 2, 1e300, 0.1]}
+
+
+def select_at(src_ptr, shape, ld, src, rows, cols, dst, ld_dst, lead=0):
+    """cyto_select into a FILL-ed buffer whose Gs x ld_dst matrix begins `lead` elements in and is followed by 5 more; returns
+    (status, the Gs x Cs block, inexact) after asserting that every byte outside the block still holds FILL."""
+    Gs = shape[0] if rows is None else len(rows)
+    Cs = shape[1] if cols is None else len(cols)
+    dt = np.dtype(DST[dst][0])
+    n = lead + Gs * ld_dst + 5
+    out = _lib.DeviceBuffer.from_numpy(np.full(n * dt.itemsize, FILL, np.uint8))
+    bad = ctypes.c_int64(-7)
+    try:
+        st = _lib.lib().cyto_select(shape[0], shape[1], src_ptr, ld, SRC[src][1], _ptr(rows), Gs, _ptr(cols), Cs, out.ptr + lead * dt.itemsize,
+                                    ld_dst, DST[dst][1], ctypes.byref(bad), 0, None)
+        raw = out.to_numpy((n * dt.itemsize,), np.uint8)
+    finally:
+        out.free()
+    body = raw.view(dt)[lead:lead + Gs * ld_dst].reshape(Gs, ld_dst)
+    mask = np.zeros(n, bool)
+    mask[lead:lead + Gs * ld_dst].reshape(Gs, ld_dst)[:, :Cs] = True
+    assert (raw[~np.repeat(mask, dt.itemsize)] == FILL).all(), (src, dst, shape, ld_dst, lead, "bytes outside the block written")
+    return st, np.ascontiguousarray(body[:, :Cs]), bad.value
+
+
+def check_select_at(src_ptr, host, shape, ld, src, rows, cols, dst, ld_dst, lead=0):
+    view = host[:shape[0], :shape[1]][np.ix_(np.arange(shape[0]) if rows is None else rows, np.arange(shape[1]) if cols is None else cols)]
+    st, block, bad = select_at(src_ptr, shape, ld, src, rows, cols, dst, ld_dst, lead)
+    tag = (src, dst, shape, ld, ld_dst, lead, None if rows is None else len(rows), None if cols is None else len(cols))
+    assert st == 0, tag
+    want, ok, defined = expect(view, dst)
+    assert bad == int(np.count_nonzero(~ok)), (tag, bad)
+    wrong = (block.view(np.uint8).reshape(block.shape + (-1,)) != want.view(np.uint8).reshape(want.shape + (-1,))).any(-1) & defined
+    assert not wrong.any(), (tag, f"{wrong.sum()} elements differ; rows {np.flatnonzero(wrong.any(1))[:8]}, columns {np.flatnonzero(wrong.any(0))[:8]}")
+    return block, defined
+
+
+def expect_range(view):
+    """What cyto_value_range reports for the view, from numpy."""
+    if view.dtype.kind in "iu":
+        return dict(lo=float(int(view.min())), hi=float(int(view.max())), ilo=int(view.min()), ihi=int(view.max()), non_integral=0, non_finite=0,
+                    not_f32_exact=int(np.count_nonzero(~survives(view, "float32"))))
+    v = view.astype(np.float64)
+    with np.errstate(all="ignore"):
+        fin = np.isfinite(v)
+        return dict(lo=float(np.nanmin(v)), hi=float(np.nanmax(v)), ilo=0, ihi=0, non_finite=int(np.count_nonzero(~fin)),
+                    non_integral=int(np.count_nonzero(fin & (np.trunc(v) != v))),
+                    not_f32_exact=int(np.count_nonzero(~np.isnan(v) & (v.astype(np.float32).astype(np.float64) != v))))
+
+
+TALL_G, TALL_C, TALL_LD = 4100, 9, 16
+TALL_ROWS = (0, 255, 256, 4095, 4096, 4099)
+
+
+def _tall(name):
+    """4 100 x 9 with ld = 16: every element of the table differs from every other (9 i + j + 300), so a row that is skipped, read
+    twice or written to another place shows; rows 0, 255, 256, 4095, 4096 and 4099 hold the planted values of the type.  The
+    table's minimum, its maximum and (float64) a value that float32 does not hold lie in rows 4096 and 4099 only."""
+    dt = SRC[name][0]
+    a = np.full((TALL_G, TALL_LD), 77 if name == "uint16" else np.nan, dt)
+    a[:, :TALL_C] = (9 * np.arange(TALL_G)[:, None] + np.arange(TALL_C)[None, :] + 300).astype(dt)
+    planted = [v for v in PLANTED[name] if v == v and abs(v) != np.inf and v not in (0, 65535, 1e300, -1)]
+    for k, r in enumerate(TALL_ROWS):
+        for j in range(0, TALL_C, 2):
+            a[r, j] = planted[(3 * k + j) % len(planted)]
+    if name == "uint16":
+        a[4096, 4], a[4099, 7] = 0, 65535
+    else:
+        a[4096, 4], a[4099, 7], a[4099, 3], a[4096, 1] = -1, 1e300, 0.1, 2.0**53 + 2
+    return np.ascontiguousarray(a)
+
+
+@pytest.fixture(scope="module")
+def tall_sources(hip_lib):
+    host = {name: _tall(name) for name in ("uint16", "float64")}
+    bufs = {name: _lib.DeviceBuffer.from_numpy(host[name]) for name in host}
+    yield host, bufs
+    for b in bufs.values():
+        b.free()
+
+
+def _tall_row_lists():
+    rng = np.random.default_rng(21)
+    full = rng.permutation(TALL_G).astype(np.int64)
+    full[rng.integers(0, TALL_G, 40)] = rng.integers(0, TALL_G, 40)              # a permutation with repeats
+    full[[0, 4095, 4096, 4099]] = (4099, 0, 4095, 4096)                           # the planted rows at both ends of the grid and behind it
+    short = np.ascontiguousarray(full[:4097])
+    short[4096] = 4099                                                           # position 4096: the one row of the second trip of the loop
+    return {"no list": None, "4100 positions": full, "4097 positions": short}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("src", ["uint16", "float64"])
+def test_select_walks_every_row_beyond_the_grid(src, tall_sources):
+    """MAX_ROW_BLOCKS = 4096: with more rows than that -- every real table -- a workgroup walks its rows in a stride loop."""
+    host, bufs = tall_sources
+    cols = np.array([8, 0, 3, 3, 7, 1, 8, 2, 4, 5, 6], np.int64)
+    for rname, rows in _tall_row_lists().items():
+        Gs = TALL_G if rows is None else len(rows)
+        assert Gs > 4096
+        for dst in (("uint16", "int64", "uint8") if src == "uint16" else ("float64", "float32", "uint16")):
+            check_select_at(bufs[src].ptr, host[src], (TALL_G, TALL_C), TALL_LD, src, rows, None, dst, 16)      # the 16-byte form
+            check_select_at(bufs[src].ptr, host[src], (TALL_G, TALL_C), TALL_LD, src, rows, None, dst, TALL_C + 2)
+            check_select_at(bufs[src].ptr, host[src], (TALL_G, TALL_C), TALL_LD, src, rows, cols, dst, len(cols) + 2)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("src", ["uint16", "float64"])
+def test_value_range_walks_every_row_beyond_the_grid(src, tall_sources):
+    """RANGE_ROW_BLOCKS = 256.  The view's minimum and maximum (and, float64, a value float32 does not hold) lie in rows >= 4096 of
+    the table, at list positions the first trip of the loop does not reach wherever the list is longer than the grid."""
+    host, bufs = tall_sources
+    rng = np.random.default_rng(22)
+    low = rng.permutation(4096)[:300].astype(np.int64)
+    lists = {256: np.r_[low[:254], 4096, 4099], 257: np.r_[low[:255], 4096, 4099], 4100: None,
+             "4100 listed": np.r_[rng.permutation(4096), 4096, 4097, 4098, 4099].astype(np.int64)}
+    cols = np.array([7, 4, 3, 1, 0, 7], np.int64)
+    table = host[src][:, :TALL_C]
+    for name, rows in lists.items():
+        rows = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64)
+        assert rows is None or len(rows) == (name if isinstance(name, int) else 4100)
+        for c in (None, cols):
+            r_, c_ = (np.arange(TALL_G) if rows is None else rows), (np.arange(TALL_C) if c is None else c)
+            want = expect_range(table[np.ix_(r_, c_)])
+            inside = table[np.ix_(r_[r_ < 4096], c_)]
+            assert inside.min() > want["lo"] and inside.max() < want["hi"]           # (the extremes are in rows >= 4096 only)
+            assert src == "uint16" or want["not_f32_exact"] > expect_range(inside)["not_f32_exact"]
+            assert value_range(bufs[src].ptr, (TALL_G, TALL_C), TALL_LD, src, rows, c) == want, (src, name, c is not None)
+
+
+EDGE_G, EDGE_C, EDGE_LD = 3, 2056, 2064          # (2064 elements: a multiple of 16 bytes in every source type)
+EDGE_CS = sorted(set([1, 63, 64, 65, 128, 129, 256, 257] + list(range(2, 18)) + [127, 130, 131, 255, 258, 259, 511, 512, 513, 515, 519, 1023,
+                                                                                   1024, 1025, 1027, 1031, 2049, 2051, 2055]))
+
+
+def _edge(name, ld=EDGE_LD):
+    dt = SRC[name][0]
+    rng = np.random.default_rng(30 + sorted(SRC).index(name))
+    a = rng.poisson(3.0, (EDGE_G, ld)).astype(dt)
+    planted = PLANTED[name]
+    where = rng.permutation(EDGE_G * EDGE_C)[:40 * len(planted)]
+    for k, w in enumerate(where):
+        a[w // EDGE_C, w % EDGE_C] = planted[k % len(planted)]
+    a[:, EDGE_C:] = 77 if name in ("uint16", "int64") else np.nan
+    return np.ascontiguousarray(a)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("src", sorted(SRC))
+def test_lane_and_workgroup_edges(src, hip_lib):
+    """Workgroups of 64, 128 and 256 lanes (lanes <= 64, <= 128, more), in the one-element form (a lane per column: Cs around 64, 128,
+    256) and in the 16-byte form (a lane per VEC = 16 / element size columns: Cs around 64 VEC and 128 VEC), whose last lane is
+    partial wherever Cs is no multiple of VEC -- 8 k + 1 ... 8 k + 7 for uint16, 4 k + 1 ... 3 for float32, odd for the 8-byte types."""
+    host = _edge(src)
+    buf = _lib.DeviceBuffer.from_numpy(host)
+    rng = np.random.default_rng(31)
+    dsts = {"uint16": ("uint16", "int64"), "int64": ("int64", "uint8"), "float32": ("float32", "float64"), "float64": ("float64", "uint16")}[src]
+    try:
+        assert buf.ptr % 16 == 0
+        for Cs in EDGE_CS:
+            cols = np.ascontiguousarray(np.r_[rng.integers(0, EDGE_C, Cs - 1), EDGE_C - 1][::-1].astype(np.int64))
+            for dst in dsts:
+                # without a list the view is the first Cs columns of a table of that width: ld_dst a multiple of 16 bytes (the 16-byte
+                # form where Cs >= VEC), and not
+                check_select_at(buf.ptr, host, (EDGE_G, Cs), EDGE_LD, src, None, None, dst, Cs + 16 + (-Cs) % 16)
+                check_select_at(buf.ptr, host, (EDGE_G, Cs), EDGE_LD, src, None, None, dst, Cs + 1 + Cs % 2)
+                check_select_at(buf.ptr, host, (EDGE_G, EDGE_C), EDGE_LD, src, None, cols, dst, Cs + 3)
+            view = host[:, :Cs]
+            assert value_range(buf.ptr, (EDGE_G, Cs), EDGE_LD, src, None, None) == expect_range(view), (src, Cs)
+            assert value_range(buf.ptr, (EDGE_G, EDGE_C), EDGE_LD, src, None, cols) == expect_range(host[:, :EDGE_C][:, cols]), (src, Cs)
+    finally:
+        buf.free()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("src", sorted(SRC))
+def test_each_precondition_of_the_16_byte_form_alone(src, hip_lib):
+    """launch_select takes the 16-byte form where the source base, ld_src, the destination base and ld_dst are all aligned for it.  Each
+    of the four is broken alone: the same bits, and nothing outside the block is written."""
+    item = np.dtype(SRC[src][0]).itemsize
+    Cs = 1031
+    host = _edge(src)
+    odd = _edge(src, 2057)
+    odd[:, :EDGE_C] = host[:, :EDGE_C]
+    assert (EDGE_LD * item) % 16 == 0 and (2057 * item) % 16 != 0
+    buf, obuf = _lib.DeviceBuffer.from_numpy(host), _lib.DeviceBuffer.from_numpy(odd)
+    try:
+        for dst in sorted(DST):
+            aligned, defined = check_select_at(buf.ptr, host, (EDGE_G, Cs), EDGE_LD, src, None, None, dst, 1040)
+            variants = {"ld_src": check_select_at(obuf.ptr, odd, (EDGE_G, Cs), 2057, src, None, None, dst, 1040),
+                        "destination base": check_select_at(buf.ptr, host, (EDGE_G, Cs), EDGE_LD, src, None, None, dst, 1040, lead=1),
+                        "ld_dst": check_select_at(buf.ptr, host, (EDGE_G, Cs), EDGE_LD, src, None, None, dst, 1033)}
+            for name, (block, _) in variants.items():
+                assert np.array_equal(block.view(np.uint8)[np.repeat(defined, block.itemsize, 1)],
+                                      aligned.view(np.uint8)[np.repeat(defined, block.itemsize, 1)]), (src, dst, name)
+            # the source base one element in: the view is then the columns 1 ... Cs of the table
+            shifted, d2 = check_select_at(buf.ptr + item, host[:, 1:], (EDGE_G, Cs - 1), EDGE_LD, src, None, None, dst, 1040)
+            m = np.repeat(defined[:, 1:] & d2, shifted.itemsize, 1)
+            assert np.array_equal(shifted.view(np.uint8)[m], np.ascontiguousarray(aligned[:, 1:]).view(np.uint8)[m]), (src, dst, "source base")
+    finally:
+        buf.free()
+        obuf.free()
