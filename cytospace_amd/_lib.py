@@ -181,6 +181,10 @@ def lib():
         L.cyto_ctx_create_ex.argtypes = [i32, i32, ctypes.POINTER(Matrix), i32, ctypes.POINTER(Matrix), i32, i32, vp, i32, i32, i32,
                                          ctypes.POINTER(vp), dp]
         L.cyto_ctx_create_ex.restype = ctypes.c_int
+        L.cyto_normalized_colsums.argtypes = [i32, i32, ctypes.POINTER(Matrix), vp, i32, vp]
+        L.cyto_normalized_colsums.restype = ctypes.c_int
+        L.cyto_normalized_colsums_timed.argtypes = [i32, i32, ctypes.POINTER(Matrix), vp, i32, vp, dp]
+        L.cyto_normalized_colsums_timed.restype = ctypes.c_int
         L.cyto_csc_to_dense_f32.argtypes = [i32, i32, i64, vp, vp, vp, vp, i64, i32, vp]
         L.cyto_csc_to_dense_f32.restype = ctypes.c_int
         L.cyto_ctx_assign_chunks.argtypes = [vp, i32, ctypes.POINTER(Chunk), i32]

@@ -35,7 +35,49 @@ def normalize_data(data, device_id=0):
     return out
 
 
-METRICS = {"Pearson_correlation": 0, "Spearman_correlation": 1, "Euclidean": 2}   # CYTO_METRIC_*
+def normalized_column_sums(data, device_id=0, return_kernel_ms=False):
+    """`normalize_data(data).sum(axis=0, dtype=float)` -- the same float64[C], bit for bit -- computed on the GPU without the
+    normalised matrix (C ABI: cyto_normalized_colsums): the counts go up in the narrowest dtype that holds them
+    (cytospace._counts_matrix) and C doubles come back.  data: a 2-D genes x columns array, or a resident.DeviceFrame, which is read
+    where it lies (gathered on the device first when it is a view or of another dtype than its narrowest; nothing is fetched).
+    return_kernel_ms: also return the HIP-event time of the summing kernel.
+
+    The kernel adds a column's genes in ascending order, which is numpy's order whenever there are two columns or more.  A table of
+    ONE column is a contiguous vector to numpy, which adds such a vector pairwise, in blocks that depend on its buffer size: there
+    numpy itself adds the G numbers of normalize_data (the values are fetched if they are a DeviceFrame's; kernel time 0)."""
+    from . import cytospace, resident
+    mat = None
+    if not resident.is_frame(data):
+        data = np.asarray(data)
+    if data.shape[1:] == (1,) and data.shape[0] > 0:
+        x = data.to_numpy() if resident.is_frame(data) else data
+        out = normalize_data(x.astype(float), device_id).sum(axis=0, dtype=float)
+        return (out, 0.0) if return_kernel_ms else out
+    if resident.is_frame(data):
+        G, C = data.shape
+        if G > 0 and C > 0:
+            m, mat = cytospace._resident_matrix(data)
+    else:
+        x = np.asarray(data)
+        if x.ndim != 2:
+            raise ValueError("expected a 2-D genes x columns matrix")
+        x, code = cytospace._boundary_matrix(cytospace._counts_matrix(x))
+        G, C = x.shape
+        m = cytospace._matrix_struct(x, code)
+    if G <= 0 or C <= 0:
+        raise ValueError("expected a genes x columns matrix with at least one gene and one column")
+    out = np.empty(C, np.float64)
+    ms = ctypes.c_double()
+    try:
+        _lib.check(_lib.lib().cyto_normalized_colsums_timed(G, C, ctypes.byref(m), out.ctypes.data, device_id, None,
+                                                            ctypes.byref(ms) if return_kernel_ms else None))
+    finally:
+        if mat is not None:
+            mat.close()
+    return (out, ms.value) if return_kernel_ms else out
+
+
+METRICS ={"Pearson_correlation": 0, "Spearman_correlation": 1, "Euclidean": 2}   # CYTO_METRIC_*
 
 
 def is_sparse(x):

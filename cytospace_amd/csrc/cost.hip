@@ -321,6 +321,50 @@ __global__ __launch_bounds__(256) void normalize_write(int G, int C, const TIn *
     for (int g = g0; g < g1; g++) y[(int64_t)g * ldy + c] = normalized<TIn>(x[(int64_t)g * ldx + c], scale, false);
 }
 
+// out[c] = the sum over the genes of normalize_write's y[g][c], added in ascending g, one float64 add per gene: the bits of numpy's
+// `.sum(axis=0)` of the C-contiguous matrix (it adds the rows in order, no pairwise tree) -- without the matrix.  The serial part is
+// that one add; the expensive part is the library log2 (~120 f64 instructions), so it is the log2 that runs wide: a block of four
+// waves owns CB columns and a tile of NCS_U * (256 / CB) genes -- thread t the column t % CB (lanes are columns: a row's reads
+// coalesce) and the gene rows t / CB + k * (256 / CB) -- writes the tile's y to LDS, and the first CB threads add it row by row while
+// the others are already computing the next tile (two tiles: the barrier after tile i + 1 is written also says tile i was read).
+// A narrow table takes a small CB: S = 5 000 spots are 313 blocks of 16 columns, each with 64 genes in flight.  Nothing depends on
+// CB, on the pitch or on the base's alignment: a column per lane, element loads.  The sum starts from -0.0, as numpy's starts from
+// row 0 itself: (-0.0) + y is y for every y.
+constexpr int NCS_U = 4;   // row groups per tile = independent log2 evaluations a thread has in flight
+template <typename TIn, int CB>
+__global__ __launch_bounds__(256) void normalized_colsum(int G, int C, const TIn *__restrict__ x, int64_t ldx,
+                                                         const double *__restrict__ colsum, double *__restrict__ out) {
+    constexpr int RB = 256 / CB, TR = RB * NCS_U;                   // genes per row group, per tile
+    __shared__ double tile[2][TR][CB];
+    const int col = threadIdx.x % CB, r = threadIdx.x / CB;
+    const int c = (int)blockIdx.x * CB + col;
+    const bool act = c < C, adder = threadIdx.x < CB;
+    const double scale = act ? 1e6 / colsum[c] : 1.0;
+    double s = -0.0;
+    int buf = 0;
+    for (int g0 = 0; g0 < G; g0 += TR, buf ^= 1) {
+        TIn v[NCS_U];
+#pragma unroll
+        for (int u = 0; u < NCS_U; u++) {
+            const int g = g0 + u * RB + r;
+            v[u] = (act && g < G) ? x[(int64_t)g * ldx + c] : (TIn)0;    // (a row past G: computed, never added)
+        }
+#pragma unroll
+        for (int u = 0; u < NCS_U; u++) tile[buf][u * RB + r][col] = normalized<TIn>(v[u], scale, false);
+        __syncthreads();
+        if (adder) {
+            const int n = min(TR, G - g0);
+            if (n == TR) {
+#pragma unroll
+                for (int k = 0; k < TR; k++) s += tile[buf][k][col];
+            } else {
+                for (int k = 0; k < n; k++) s += tile[buf][k][col];
+            }
+        }
+    }
+    if (adder && act) out[c] = s;
+}
+
 // partial column sums of squares of a float32 matrix (the rounded values the matrix cores will see)
 __global__ __launch_bounds__(256) void colsq_partial(int G, int C, const float *__restrict__ z, int64_t ldz, double *__restrict__ part) {
     const int c = blockIdx.x * 256 + threadIdx.x;
@@ -737,6 +781,46 @@ static int standardize_any(int dt, int G, int C, const void *dx, int64_t ldx, in
     }
 }
 
+// The column sums of the normalised matrix (cyto_normalized_colsums) of a device matrix, brought to the host: colsum by the two
+// kernels normalize_data's own colsum comes from, then normalized_colsum.  Temporaries: the column-sum partials and 2 C doubles.
+template <typename TIn>
+static int normalized_colsums_dev(int G, int C, const TIn *dx, int64_t ldx, double *sums, int device_id, hipStream_t stream,
+                                  double *kernel_ms) {
+    const int nblk = (G + TGB - 1) / TGB;
+    DevBuf part, colsum, out;
+    int rc;
+    if ((rc = part.alloc((size_t)nblk * C * sizeof(double), stream)) || (rc = colsum.alloc((size_t)C * sizeof(double), stream)) ||
+        (rc = out.alloc((size_t)C * sizeof(double), stream)))
+        return rc;
+    Events<2> ev;
+    if (kernel_ms && (rc = ev.create())) return rc;
+    // (the column-sum pass as standardize_dev launches it: quads where every row can be read as quads -- the same sums either way)
+    const bool vec = C % 4 == 0 && ldx % 4 == 0 && (reinterpret_cast<uintptr_t>(dx) % (sizeof(TIn) >= 4 ? 16 : 4 * sizeof(TIn))) == 0;
+    const dim3 grid((C + (vec ? 256 : 64) - 1) / (vec ? 256 : 64), nblk), blk(64 * TRS);
+    if (vec) hipLaunchKernelGGL((colsum_partial_v<TIn, 4>), grid, blk, 0, stream, G, C, dx, ldx, part.as<double>());
+    else hipLaunchKernelGGL((colsum_partial_v<TIn, 1>), grid, blk, 0, stream, G, C, dx, ldx, part.as<double>());
+    hipLaunchKernelGGL(col_finish_sum, dim3((C + 255) / 256), dim3(256), 0, stream, C, nblk, part.as<double>(), colsum.as<double>());
+    if (kernel_ms) CYTO_HIP(hipEventRecord(ev[0], stream));
+    // columns per block: the widest of 64 / 32 / 16 that still gives every CU two blocks; 16 for anything narrower
+    const int want = 2 * device_cus(device_id);
+    if ((C + 63) / 64 >= want)
+        hipLaunchKernelGGL((normalized_colsum<TIn, 64>), dim3((C + 63) / 64), dim3(256), 0, stream, G, C, dx, ldx, colsum.as<double>(), out.as<double>());
+    else if ((C + 31) / 32 >= want)
+        hipLaunchKernelGGL((normalized_colsum<TIn, 32>), dim3((C + 31) / 32), dim3(256), 0, stream, G, C, dx, ldx, colsum.as<double>(), out.as<double>());
+    else
+        hipLaunchKernelGGL((normalized_colsum<TIn, 16>), dim3((C + 15) / 16), dim3(256), 0, stream, G, C, dx, ldx, colsum.as<double>(), out.as<double>());
+    if (kernel_ms) CYTO_HIP(hipEventRecord(ev[1], stream));
+    CYTO_HIP(hipGetLastError());
+    CYTO_HIP(hipMemcpyAsync(sums, out.p, (size_t)C * sizeof(double), hipMemcpyDeviceToHost, stream));
+    CYTO_HIP(hipStreamSynchronize(stream));   // the temporaries above die with this scope
+    if (kernel_ms) {
+        float ms = 0.f;
+        CYTO_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        *kernel_ms = ms;
+    }
+    return CYTO_OK;
+}
+
 }  // namespace cyto
 
 using namespace cyto;
@@ -756,6 +840,36 @@ int cyto_normalize_data(int G, int C, const void *x, int64_t ldx, int x_is_f64, 
     if ((rc = standardize_any(x_is_f64, G, C, dx.p, C, 0, nullptr, 0, dy.as<double>(), C, nullptr, 0))) return rc;
     CYTO_HIP(hipMemcpy2D(out, (size_t)ldo * 8, dy.p, (size_t)C * 8, (size_t)C * 8, G, hipMemcpyDeviceToHost));
     return CYTO_OK;
+}
+
+// estimate_cell_number_RNA_reads' `normalize_data(x).sum(axis=0)` (cytospace/cytospace.py:116-134) without the normalised matrix:
+// the same float64 numbers, bit for bit (normalized_colsum).  kernel_ms (optional): HIP-event time of that kernel.
+int cyto_normalized_colsums_timed(int G, int C, const cyto_matrix *x, double *sums, int device_id, void *stream_, double *kernel_ms) {
+    if (G <= 0 || C <= 0 || !x || !x->data || !sums || x->ld < C || !dtype_ok(x->is_f64)) return CYTO_ERR_BAD_ARG;
+    int rc = select_device(device_id);
+    if (rc) return rc;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const int dt = x->is_f64;
+    const size_t esz = dtype_size(dt);
+    DevBuf dx;
+    const void *src = x->data;
+    int64_t sld = x->ld;
+    if (!x->on_device) {
+        if ((rc = dx.alloc((size_t)G * C * esz, stream))) return rc;
+        CYTO_HIP(hipMemcpy2DAsync(dx.p, (size_t)C * esz, x->data, (size_t)x->ld * esz, (size_t)C * esz, G, hipMemcpyHostToDevice, stream));
+        src = dx.p;
+        sld = C;
+    }
+    switch (dt) {
+    case CYTO_DTYPE_F64: return normalized_colsums_dev<double>(G, C, (const double *)src, sld, sums, device_id, stream, kernel_ms);
+    case CYTO_DTYPE_U16: return normalized_colsums_dev<uint16_t>(G, C, (const uint16_t *)src, sld, sums, device_id, stream, kernel_ms);
+    case CYTO_DTYPE_U8: return normalized_colsums_dev<uint8_t>(G, C, (const uint8_t *)src, sld, sums, device_id, stream, kernel_ms);
+    default: return normalized_colsums_dev<float>(G, C, (const float *)src, sld, sums, device_id, stream, kernel_ms);
+    }
+}
+
+int cyto_normalized_colsums(int G, int C, const cyto_matrix *x, double *sums, int device_id, void *stream) {
+    return cyto_normalized_colsums_timed(G, C, x, sums, device_id, stream, nullptr);
 }
 
 // A1+A2 (first half): per-column normalise (unless already_normalized) and standardise; writes the

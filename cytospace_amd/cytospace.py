@@ -653,13 +653,17 @@ def apply_linear_assignment(scRNA_data, st_data, coordinates_data, cell_number_t
 
 # ---- upstream of the chunk fan-out: the per-spot cell counts, the per-type cell numbers and the
 # cell sampler whose output apply_linear_assignment consumes.  Host code like the reference's; the one heavy step of
-# the first (normalize_data over the whole ST matrix) runs on the device. ----
+# the first (the column sums of the normalised ST matrix) runs on the device. ----
 
 def estimate_cell_number_RNA_reads(st_data, mean_cell_numbers, device_id=0):
     """cytospace/cytospace.py:116-134.  Cells per spot from a straight line through (min, 0 or 1) and
-    (mean, mean_cell_numbers) of the per-spot sums of the normalised expression; truncated to int."""
+    (mean, mean_cell_numbers) of the per-spot sums of the normalised expression; truncated to int.  st_data: a DataFrame, or a
+    resident.DeviceFrame (read on the device, nothing fetched).  The sums are those of
+    `normalize_data(st_data.values.astype(float)).sum(axis=0, dtype=float)`, bit for bit, computed on the device
+    (common.normalized_column_sums): the normalised matrix is never written."""
     from . import common
-    reads = common.normalize_data(st_data.values.astype(float), device_id).sum(axis=0, dtype=float)
+    from .resident import is_frame
+    reads = common.normalized_column_sums(st_data if is_frame(st_data) else st_data.values, device_id)
     lo, mid = reads.min(), reads.mean()
     line = np.poly1d(np.polyfit(np.array([lo, mid]), np.array([1 if lo > 0 else 0, mean_cell_numbers]), 1))
     return line(reads).astype(int)

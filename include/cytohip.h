@@ -87,6 +87,7 @@ int cyto_cache_peek(size_t bytes, void *host_out, int device_id);
  *   cyto_transform / cyto_standardize / cyto_ctx_create_ex inputs: always in place.  The four-column kernels run when the width and
  *                         ld are multiples of 4 and the base is aligned for four elements (16 bytes for float32 and float64, 8 for
  *                         uint16, 4 for uint8) -- and z_dev is 16-byte aligned with ldz % 4 == 0; otherwise a column per lane
+ *   cyto_normalized_colsums input: always in place (its column-sum pass by the same rule, its summing kernel a column per lane)
  *   cyto_cost_metric / cyto_cost_pearson operands: in place; they keep their own rule (Gpad % 32 == 0, ld % 128 == 0, the columns
  *                         between the width and the next multiple of 128 zero, as cyto_transform leaves them); cost_dev: any ldc >= C
  * Padding.  Bytes outside the n x n (nu x n, G x C) block -- the columns between the width and ld, whatever lies before the base or
@@ -433,6 +434,24 @@ typedef struct {
 } cyto_matrix;
 int cyto_ctx_create_ex(int metric, int G, const cyto_matrix *sc, int C, const cyto_matrix *st, int S, int already_normalized,
                        void *comm, int root, int rank, int device_id, cyto_expr_ctx **out, double *bcast_ms);
+
+/* ---- The per-spot reads of estimate_cell_number_RNA_reads (cytospace/cytospace.py:116-134): sums[c] = the sum over the G genes of
+ * normalize_data's column c, i.e. numpy's `normalize_data(x).sum(axis=0)`, with the SAME float64 bits -- the values
+ * cyto_normalize_data writes (the library log2, the same column sums), added in ascending gene order with one float64 add per gene,
+ * as numpy adds the rows of a C-contiguous matrix -- and without the G x C float64 matrix: nothing of that size is written to HBM
+ * or crosses PCIe; the temporaries are the column-sum partials and 2 C doubles.  (C == 1 is the one shape where numpy's order is
+ * another: a single column is a contiguous vector, which numpy adds pairwise.  This call adds in gene order for every C;
+ * common.normalized_column_sums lets numpy add a single column.)
+ *   x      G x C matrix of CYTO_DTYPE_F32 / _F64 / _U16 / _U8 (x->is_f64); the sums do not depend on the dtype where it holds the
+ *          values exactly.  on_device = 0: a host matrix, uploaded as it is.  on_device = 1: read where it lies, under the rules of
+ *          "Device inputs and caller streams" above (any ld >= C, any element-aligned base, padding never interpreted).
+ *   sums   host float64[C], filled when the call returns
+ *   stream as every `void *stream` above
+ * CYTO_ERR_BAD_ARG, before the device is touched: G <= 0, C <= 0, a null pointer, ld < C, another dtype.
+ * cyto_normalized_colsums_timed: the same call; kernel_ms (optional) = HIP-event time of the summing kernel alone (without the
+ * column-sum pass before it, the upload and the download). */
+int cyto_normalized_colsums(int G, int C, const cyto_matrix *x, double *sums, int device_id, void *stream);
+int cyto_normalized_colsums_timed(int G, int C, const cyto_matrix *x, double *sums, int device_id, void *stream, double *kernel_ms);
 
 /* SURVEY 8(f) rank 2, device-side staging: sparse counts as the reference reads them from a 10x MatrixMarket file
  * (scipy.io.mmread, cytospace/common/common.py:49; CSC: colptr[C + 1], rowidx[nnz], vals[nnz], host arrays) are uploaded as
